@@ -1,10 +1,12 @@
-"""bench.py keeps its contract: one JSON line (the last line of stdout) with the driver's fields, the roofline and,
-when asked for, the CPU baseline."""
+"""bench.py keeps its contract: one JSON line (the last line of stdout) with the driver's fields; under --full also the
+roofline, the extras and, when asked for, the CPU baseline.  A plain run measures the headline only and, with --dump-outputs,
+writes the same outputs every time."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +25,7 @@ def _run(extra, env=None):
 
 
 def test_bench_line_fields():
-    d = _run(["--cpu-seconds", "2"])
+    d = _run(["--full", "--cpu-seconds", "2"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -66,6 +68,33 @@ def test_bench_line_fields():
     assert cm["value"] > 3 * c["value"] and cm["vs_numpy_oracle_same_plugins"] == cm["value"] / c["value"]
 
 
+def test_plain_run_is_the_headline_and_its_dump_repeats(tmp_path):
+    """No --full: set-up, warm-up, the timed steps, the line -- nothing measured besides the headline; --dump-outputs writes the tree
+    the timed path left, float64, within 64 MB, identical from run to run of the same command."""
+    runs = []
+    for k in range(2):
+        out = str(tmp_path / ("run%d" % k))
+        d = _run(["--gpus", "1", "--units", "16", "--dump-outputs", out])
+        runs.append((d, {f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))}, out))
+    d, dump, out = runs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True and d["value"] > 1e4
+    assert abs(d["ms_per_step"] * 4 - 1e3 * d["timed_region_s"]) < 1e-6 * d["ms_per_step"]
+    for k in ("roofline", "cpu_baseline", "repeats", "effective_mhz", "steer_kernel", "synchronous_mode", "seed_spread",
+              "multi_tree", "dominant_kernel", "chain_bound", "callback_mode"):
+        assert k not in d, k
+    assert all(a.dtype == np.float64 for a in dump.values())
+    assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64 * 2 ** 20
+    n = len(dump["node_ids"])
+    lo, hi = d["config"]["nodes_window"]
+    assert lo <= n <= hi and dump["tree_states"].shape == (n, 6) and dump["tree_gains"].shape == (n, 3, 6)
+    assert dump["tree_parents"][0] == -1 and np.all(dump["tree_parents"][1:] < np.arange(1, n))
+    assert dump["last_step_counts"][0] == d["config"]["attempts_per_step"]
+    other = runs[1][1]
+    assert sorted(other) == sorted(dump) and all(np.array_equal(dump[k], other[k]) for k in dump)
+
+
 def test_bench_sharded_code_path_world_of_one():
     d = _run(["--no-cpu", "--no-extras"], env={"LQRRT_FORCE_SHARDED": "1"})
     assert d["value"] > 1e4 and "cpu_baseline" not in d
@@ -77,7 +106,7 @@ def test_bench_sharded_run_reports_four_curves():
     """A sharded run (here: a world of one through the native loop and a real RCCL communicator) prints, next to the exact-mode
     value, the synchronous mode sample-sharded, BASELINE config 5 tree-sharded and -- the one that scales -- a fleet of independent
     planners per device."""
-    d = _run(["--no-cpu", "--units", "16"], env={"LQRRT_FORCE_SHARDED": "1"})
+    d = _run(["--full", "--no-cpu", "--units", "16"], env={"LQRRT_FORCE_SHARDED": "1"})
     assert "native loop" in d["config"]["parallelism"]
     assert d["synchronous_mode"]["value"] > d["value"] and "sample-sharded" in d["synchronous_mode"]["parallelism"]
     c5 = d["config5_tree_sharded"]
@@ -89,7 +118,7 @@ def test_bench_sharded_run_reports_four_curves():
 def test_bench_config5_workload():
     """BASELINE config 5 (100k boxes, 50k-node window) through the same harness, single GPU and the tree-sharded
     N>1 code path in a world of one."""
-    d = _run(["--workload", "cfg5", "--units", "4", "--cpu-seconds", "3"])
+    d = _run(["--full", "--workload", "cfg5", "--units", "4", "--cpu-seconds", "3"])
     assert d["config"]["workload"] == "double_integrator_100k_boxes_50k" and d["config"]["nodes_window"] == [47500, 52500]
     assert d["value"] > 1e4 and d["cpu_baseline"]["c_oracle_value"] > 0
     d = _run(["--workload", "cfg5", "--units", "4", "--no-cpu", "--no-extras"], env={"LQRRT_FORCE_SHARDED": "1"})

@@ -9,7 +9,7 @@ for seed in ${AB_SEEDS:-1}; do
   for so in variants/*.so; do
     for kv in "$@"; do
       if [ "$kv" = "-" ]; then envs=""; else envs="${kv//,/ }"; fi
-      env $envs LQRRT_LIB=$PWD/$so python bench.py --no-cpu --seed $seed ${AB_ARGS:---steps 10 --warmup 2 --repeats 1} 2>/dev/null | python -c "
+      env $envs LQRRT_LIB=$PWD/$so python bench.py --full --no-cpu --seed $seed ${AB_ARGS:---steps 10 --warmup 2 --repeats 1} 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 sk=d['steer_kernel']

@@ -6,11 +6,11 @@ mkdir -p gpurun_out
 : > gpurun_out/ab_wg4.txt
 for r in 1 2; do
 for v in 0 1; do
-  LQRRT_NN_WG4=$v python bench.py --no-cpu --steps 10 --warmup 2 --repeats 1 2>/dev/null | python -c "
+  LQRRT_NN_WG4=$v python bench.py --full --no-cpu --steps 10 --warmup 2 --repeats 1 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('WG4=$v cfg4 exact %d | sync %d | scan avg launch %.2f us' % (d['value'], d['synchronous_mode']['value'], d['roofline']['avg_launch_us']))" >> gpurun_out/ab_wg4.txt
-  LQRRT_NN_WG4=$v python bench.py --no-cpu --no-extras --workload cfg5 --units 32 --steps 6 --warmup 1 --repeats 1 2>/dev/null | python -c "
+  LQRRT_NN_WG4=$v python bench.py --full --no-cpu --no-extras --workload cfg5 --units 32 --steps 6 --warmup 1 --repeats 1 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('WG4=$v cfg5 exact %d | scan avg launch %.2f us' % (d['value'], d['roofline']['avg_launch_us']))" >> gpurun_out/ab_wg4.txt

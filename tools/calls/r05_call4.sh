@@ -10,7 +10,7 @@ echo "== multi_bench" >> $O
 timeout 900 python tools/multi_bench.py --trees 1,2,4,8,16,32 --steps 4 >> $O 2>gpurun_out/r05_call4_multi.err
 tail -5 gpurun_out/r05_call4_multi.err >> $O
 echo "== bench sanity (refactored kernels)" >> $O
-timeout 300 python bench.py --no-cpu --steps 10 --warmup 2 --repeats 1 2>/dev/null | python -c "
+timeout 300 python bench.py --full --no-cpu --steps 10 --warmup 2 --repeats 1 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('cfg4 value=%d scan_us=%.2f steer_us=%.2f sync=%d' % (d['value'], d['roofline']['avg_launch_us'], d['steer_kernel']['avg_launch_us'], d['synchronous_mode']['value']))" >> $O

@@ -18,7 +18,7 @@ for b in launch_floor launch_chain issue barrier; do
 done
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $O/bench_plain.json 2> $O/bench_plain.err < /dev/null
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_plain.json 2> $O/bench_plain.err < /dev/null
 CMD="python $R/bench.py --steps 3 --warmup 1 --units 16 --no-cpu --no-extras"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $CMD > $O/bench_under_rocprof.json 2> $O/stats.log < /dev/null
 find $O/stats -name "bench_kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
@@ -73,7 +73,7 @@ tail -c 400 $O/bench_plain.json
 $R/tools/micro/issue.bin > $O/issue.txt 2>&1
 $R/tools/micro/barrier.bin > $O/barrier.txt 2>&1
 # 10. the N > 1 code path on this one GPU: native sharded loop, real RCCL communicator, world of one (+ its two extra curves)
-LQRRT_FORCE_SHARDED=1 timeout 600 python $R/bench.py --steps 20 --warmup 5 --no-cpu > $O/bench_forced_sharded.json 2> $O/bench_forced_sharded.err < /dev/null
+LQRRT_FORCE_SHARDED=1 timeout 600 python $R/bench.py --full --steps 20 --warmup 5 --no-cpu > $O/bench_forced_sharded.json 2> $O/bench_forced_sharded.err < /dev/null
 # 11. every BASELINE configuration + the two Riccati systems; busy / gap breakdown of the loop's kernel timeline
 timeout 600 python $R/tools/run_configs.py 2>&1 | grep -v amdgpu.ids > $O/configs.txt
 bash $R/tools/timeline.sh > /dev/null 2>&1; python $R/tools/timeline_report.py $R/gpurun_out/kt_tail.csv > $O/timeline.txt 2>&1

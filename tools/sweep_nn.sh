@@ -10,7 +10,7 @@ for w in 1024 2048 4096 8192; do for c in 16 32 64; do
 import sys, json
 for l in sys.stdin:
     d = json.loads(l); print('   W=%4d %6.2f us  %.2f Tpairs/s' % (d['W'], d['launch_us'], d['pairs_per_s'] / 1e12))" >> $O
-  LQRRT_NN_WAVES=$w LQRRT_NN_MIN_CHUNK=$c timeout 120 python bench.py --no-cpu --no-extras --steps 60 2>/dev/null | tail -1 | python -c "
+  LQRRT_NN_WAVES=$w LQRRT_NN_MIN_CHUNK=$c timeout 120 python bench.py --full --no-cpu --no-extras --steps 60 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); r = d['roofline']; print('   bench %d attempts/s, nn %.2f us' % (d['value'], r['avg_launch_us']))" >> $O
 done; done
