@@ -359,6 +359,27 @@ int lqrrt_steer_batch(lqrrt_engine* e, const int32_t* parent_dev, const double* 
 int lqrrt_steer_force(lqrrt_engine* e, int parent, const double* xtar_dev, int max_steps, double rtol, double atol,
                       int32_t* len_dev, double* xseq_dev, double* useq_dev, void* stream);
 
+/* Plan refinement (Planner.refine_plan; not in the reference).  plan_host [P] is a found plan, node ids from the root (0)
+ * down a parent chain.  Candidate (i, j), 0 <= i < j < P, starts at node plan[i] (state and gain) at cost
+ * sum_{k<=i} L_k (L_0 = 1, else the node's edge length) and steers (planner.py:354-438 with a fixed horizon of
+ * horizon_iters steps, no adaptive heuristic) toward plan[j] .. plan[P-2], then toward the goal up to goal_tries times;
+ * an empty edge adds nothing, a non-empty one moves the chain to its end state with lqr(x_end, u_last)[1].  The chain
+ * ends after the first edge ending strictly inside the goal box; if the targets run out first it is invalid.
+ *
+ * lqrrt_refine_search: the valid candidate of smallest (cost, i, j) with cost < incumbent -> *cost, *i_out, *j_out;
+ * none: *cost = incumbent, *i_out = *j_out = -1.  One launch, one wavefront per candidate; synchronous.  Plans of at most
+ * 11586 nodes (the launch's 2^32 threads; LQRRT_E_ARG above). */
+int lqrrt_refine_search(lqrrt_engine* e, const int32_t* plan_host, int P, int goal_tries, int horizon_iters,
+                        int64_t incumbent, int64_t* cost, int32_t* i_out, int32_t* j_out, void* stream);
+
+/* lqrrt_refine_commit: replays candidate (i, j) and appends its non-empty edges to the tree as a parent chain below
+ * plan[i] (state, gain, parent, edge, angle-error table; the host mirrors and the ignore set stay valid, the new nodes are
+ * not ignored).  ids_out [cap_ids >= P-1-j+goal_tries] receives the new ids; returns their count.  LQRRT_E_CAPACITY when
+ * the tree cannot hold the chain, LQRRT_E_STATE when the chain does not reach the goal: the tree is then unchanged.
+ * Synchronous. */
+int lqrrt_refine_commit(lqrrt_engine* e, const int32_t* plan_host, int P, int goal_tries, int horizon_iters, int i, int j,
+                        int32_t* ids_out, int cap_ids, void* stream);
+
 /* ---------------------------------------------------------------- wave engine -------- */
 
 /* Explicit sample stream: the caller supplies the samples (a user xrand_gen function,

@@ -195,6 +195,11 @@ struct lqrrt_engine {
     std::vector<char> proto_cache;
     hipStream_t multi_stream = nullptr;   // the stream of the group this engine leads when a multi call runs on several host threads
 
+    // plan refinement (engine_refine.hpp): the plan's ids and cost prefix [2][ref_cap], the best key and the commit's outputs
+    int* d_ref = nullptr;
+    int ref_cap = 0;
+    unsigned long long* d_ref_key = nullptr;      // [4]: the key, then the three ints of k_refine_commit's output
+
     // HBM held by this engine (lqrrt_engine_footprint): everything allocated at creation, and the H-dependent pools (alloc_wave)
     size_t bytes_fixed = 0, bytes_wave = 0, bytes_pinned = 0;
 

@@ -7,6 +7,7 @@
 //   k_feasible_batch         <- Constraints.is_feasible                   constraints.py:53-61
 //   k_tree_root / k_append   <- Tree.__init__ / Tree.add_node             tree.py:50-96
 //   k_decide                 (build-only: exact-mode wave validation, see engine.hip)
+//   k_refine_search / _commit (build-only: Planner.refine_plan, chains of k_steer's rollout over a found plan; refine.hpp)
 //
 // Execution model choices (MI355X; DESIGN.md section 4 has the measurements):
 //   * NN scan: one lane = one sample, one wavefront per workgroup, grid = (64-sample groups) x (node chunks) with an
@@ -205,5 +206,6 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "steer.hpp"      // SteerFuse, steer_body, k_steer                          <- planner.py:354-438
 #include "ops.hpp"        // batched operators, k_steer_force, k_tree_root, k_append <- constraints.py:53-61, tree.py:50-96
 #include "multi.hpp"      // k_nn_scan_multi / k_steer_multi                         (build-only: several engines per launch)
+#include "refine.hpp"     // k_refine_search / k_refine_commit                       (Planner.refine_plan: shortcuts of a found plan)
 
 }  // namespace lq

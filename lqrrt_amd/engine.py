@@ -392,6 +392,25 @@ class Engine(object):
         k = int(ln.cpu()[0])
         return xs[:k].cpu().numpy(), us[:k].cpu().numpy()
 
+    # -- plan refinement (csrc/engine_refine.hpp; the rule: tests/refine_reference.py) ---------
+    def refine_round(self, plan, horizon_iters, incumbent, goal_tries=8):
+        """One shortcut search over `plan` (node ids from the root): (cost, i, j) of the cheapest candidate whose chain reaches the
+        goal in fewer than `incumbent` steps, or None (lqrrt_refine_search)."""
+        ids = np.ascontiguousarray(plan, dtype=np.int32)
+        cost, i, j = C.c_int64(), C.c_int32(), C.c_int32()
+        nat.check(nat.lib().lqrrt_refine_search(self.h, nat.ptr(ids), len(ids), int(goal_tries), int(horizon_iters), int(incumbent),
+                                                C.byref(cost), C.byref(i), C.byref(j), self._stream()))
+        return None if i.value < 0 else (cost.value, i.value, j.value)
+
+    def refine_commit(self, plan, horizon_iters, i, j, goal_tries=8):
+        """Appends the chain of candidate (i, j) below plan[i] (lqrrt_refine_commit); returns the new node ids.  NativeError with
+        code E_CAPACITY when the tree cannot hold it (the tree is then unchanged)."""
+        ids = np.ascontiguousarray(plan, dtype=np.int32)
+        out = np.empty(max(len(ids) - 1 - int(j) + int(goal_tries), 1), dtype=np.int32)
+        k = nat.check(nat.lib().lqrrt_refine_commit(self.h, nat.ptr(ids), len(ids), int(goal_tries), int(horizon_iters), int(i), int(j),
+                                                    nat.ptr(out), len(out), self._stream()))
+        return out[:k].tolist()
+
     def push_samples(self, xs):
         xs = nat.as_f64(xs)
         if xs.ndim != 2 or xs.shape[1] != self.n:

@@ -394,6 +394,63 @@ class Planner:
             self.u_seq.extend(us)
             self.t_seq = np.arange(len(self.x_seq)) * self.dt
 
+    def refine_plan(self, max_rounds=8, goal_tries=8):
+        """
+        Shortens the plan the last update_plan found (not in the reference, whose plan is the tree path of its first goal hit).
+        One round tries every shortcut (i, j) of the plan p_0 .. p_{P-1}: from p_i, steer toward p_j .. p_{P-2} and then toward
+        the goal (up to `goal_tries` times), one _steer(force_arrive=False) edge per target with the fixed horizon
+        `horizon_iters` (no adaptive heuristic), until an edge ends inside the goal region.  The cheapest such chain (fewest
+        steps; ties to the smaller i, then j) replaces the plan after p_i if it is shorter; its edges are appended to the tree.
+        Rounds repeat until one finds nothing shorter, after `max_rounds`, or when the tree cannot hold the next chain.  The
+        search is one kernel launch per round on the device (csrc/refine.hpp); tests/refine_reference.py restates the rule.
+
+        A plan that ends in the finish_on_goal node is refined without it, and the exact-goal steer is then run again from the
+        new last node.  Returns the number of rounds accepted (0: nothing changed, e.g. no plan reached the goal).  If a native call
+        fails, the rounds accepted before it are adopted (plan, interpolators) and the error is raised.
+        """
+        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
+            raise NotImplementedError("refine_plan: in callback mode the steer is the user's Python function, which every candidate "
+                                      "of the search would have to run; the device cannot call it.")
+        if int(max_rounds) < 0 or int(goal_tries) < 1:
+            raise ValueError("max_rounds must be >= 0 and goal_tries >= 1.")
+        tree, eng = self.tree, self._engine
+        if not self.plan_reached_goal or getattr(self, "node_seq", None) is None or tree is None or not tree.on_device \
+                or tree._e is not eng:
+            return 0
+        plan = [int(v) for v in self.node_seq]
+        finish = len(plan) > 1 and plan[-1] >= eng.size                    # the finish_on_goal node lives on the host (tree.add_node)
+        if tree._host_nodes() != (1 if finish else 0):
+            raise RuntimeError("refine_plan: the tree holds nodes added with Tree.add_node; refine before adding nodes by hand.")
+        core = plan[:-1] if finish else plan
+        H = int(self.horizon_iters)
+        rounds, error = 0, None
+        while rounds < int(max_rounds):
+            try:
+                lens = eng.edge_lengths()
+                incumbent = 1 + int(sum(int(lens[p]) for p in core[1:]))
+                win = eng.refine_round(core, H, incumbent, goal_tries)
+                if win is None:
+                    break
+                _, i, j = win
+                ids = eng.refine_commit(core, H, i, j, goal_tries)
+            except (nat.NativeError, ValueError) as ex:
+                if getattr(ex, "code", None) != nat.E_CAPACITY:
+                    error = ex                                      # raised below, once the rounds already accepted are adopted
+                break
+            if rounds == 0 and finish:
+                tree._drop_host_tail()                                      # refined away; a new one follows below
+            core = core[:i + 1] + ids
+            rounds += 1
+        if rounds:
+            # the plan describes the tree as it now is, also when a later round failed (a failed commit appends nothing)
+            self._adopt_plan(core[-1])
+            if finish:
+                self._finish_on_goal()
+            self._prepare_interpolators()
+        if error is not None:
+            raise error
+        return rounds
+
     def _in_goal(self, x):
         """True if x lies strictly inside the goal box (planner.py:442-447)."""
         x = np.asarray(x, dtype=np.float64)

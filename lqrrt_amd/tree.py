@@ -208,6 +208,15 @@ class Tree:
             c[key] = (list(x), list(u))
         return c[key]
 
+    def _host_nodes(self):
+        """Number of nodes appended on the host after the device part (the finish_on_goal node, hand-built nodes)."""
+        return len(self._h_pID)
+
+    def _drop_host_tail(self):
+        """Forgets the last host-appended node (Planner.refine_plan replaces the finish_on_goal node it refined away)."""
+        for seq in (self._h_state, self._h_pID, self._h_lqr, self._h_x, self._h_u):
+            seq.pop()
+
     # -- the reference's methods ----------------------------------------------------------------------
     def add_node(self, pID, state, lqr, x_seq, u_seq):
         """
