@@ -261,6 +261,30 @@ int lqrrt_tree_append(lqrrt_engine* e, int parent, const double* state_host, con
  * plan is forgotten if its end node was dropped; a mark (lqrrt_tree_mark) beyond the new size becomes void. */
 int lqrrt_tree_truncate(lqrrt_engine* e, int size);
 
+/* Keeps the subtree below node `new_root` as the tree of the next plan, in place (Planner.replan; not in the reference, which
+ * starts every plan from one node, planner.py:172).  The rule (tests/retain_reference.py restates it):
+ *   ok[i]   = revalidate ? every recorded row of node i's edge passes the feasibility test under the engine's CURRENT geometry
+ *             (lqrrt_engine_set_geometry) : true
+ *   keep[i] = i == new_root, or i > new_root and ok[i] and keep[pID[i]]       (the root's own edge is not part of the new tree)
+ * Kept nodes are renumbered in ascending old-id order; parents are remapped; the root gets parent -1 and the one-row edge of a
+ * seed (its state, zero effort; tree.py:69-70) and keeps its gain; everything else moves bit for bit.  Goal bookkeeping
+ * (lqrrt_plan_best) and the ignore set are rebuilt against the CURRENT goal box (lqrrt_engine_set_resolution): a hit is a kept
+ * non-root node strictly inside it, best = fewest steps from the new root (its 1 included), lowest new id on ties, the ignore
+ * set = the root paths of all hits.  A mark (lqrrt_tree_mark) becomes void; the sample stream and the counters are not touched.
+ * old_to_new_host [old size] (or NULL) receives the new id of every old node, -1 = dropped.  Synchronous.  Scratch is
+ * transient (freed before returning; DESIGN.md section 10 gives its size).  LQRRT_E_ARG: no such node (tree.py:84's message);
+ * LQRRT_E_STATE: no tree / no resolution.  On a failure before the first array is moved the tree is unchanged. */
+typedef struct {
+    int32_t old_size, kept;
+    int32_t outside;          /* not in the subtree of new_root                              */
+    int32_t infeasible;       /* in the subtree, own edge fails                              */
+    int32_t orphaned;         /* in the subtree, own edge passes, an ancestor was dropped    */
+    int32_t root_feasible;    /* the test of the last row of the root's old edge (1 when revalidate == 0) */
+    int32_t goal_hits, best_end;   /* best_end / best_steps: -1 without a hit               */
+    int64_t best_steps;
+} lqrrt_retain_stats;
+int lqrrt_tree_retain(lqrrt_engine* e, int new_root, int revalidate, lqrrt_retain_stats* out, int32_t* old_to_new_host, void* stream);
+
 /* Overwrites the ignore bits of nodes [first, first+count) (planner.py:270 `ignores`). */
 int lqrrt_tree_set_ignored(lqrrt_engine* e, int first, int count, const uint8_t* flags_host);
 

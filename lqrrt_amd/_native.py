@@ -55,6 +55,15 @@ class ExtendStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RetainStats(C.Structure):
+    _fields_ = [("old_size", C.c_int32), ("kept", C.c_int32), ("outside", C.c_int32), ("infeasible", C.c_int32),
+                ("orphaned", C.c_int32), ("root_feasible", C.c_int32), ("goal_hits", C.c_int32), ("best_end", C.c_int32),
+                ("best_steps", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/lqrrt_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I, _I64, _D = C.c_int, C.c_int64, C.c_double
@@ -81,6 +90,7 @@ SIGNATURES = {
     "lqrrt_tree_append": (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
     "lqrrt_tree_truncate": (_I, [_P, _I]),
     "lqrrt_tree_set_ignored": (_I, [_P, _I, _I, _P]),
+    "lqrrt_tree_retain": (_I, [_P, _I, _I, C.POINTER(RetainStats), _P, _P]),
     "lqrrt_tree_get_edges": (_I, [_P, _I, _I, _P, _P]),
     "lqrrt_tree_mark": (_I, [_P]),
     "lqrrt_tree_rewind": (_I, [_P]),

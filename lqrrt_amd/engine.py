@@ -188,6 +188,18 @@ class Engine(object):
                                             opt(ignored, np.uint8, (N,)), self._stream()))
         self.generation += 1
 
+    def tree_retain(self, root, revalidate=True):
+        """Keeps the subtree below node `root` as the tree of the next plan, in place (lqrrt_tree_retain; the rule:
+        tests/retain_reference.py): with `revalidate` every kept edge is tested again against the engine's current geometry and
+        what hangs below a failing edge is dropped; kept nodes are renumbered in ascending order, goal bookkeeping and ignore set
+        are rebuilt against the current goal.  Returns (stats dict, old_to_new int32 array, -1 = dropped)."""
+        st = nat.RetainStats()
+        old_to_new = np.empty(max(self.size, 1), dtype=np.int32)
+        nat.check(nat.lib().lqrrt_tree_retain(self.h, int(root), 1 if revalidate else 0, C.byref(st), nat.ptr(old_to_new),
+                                              self._stream()))
+        self.generation += 1          # bound Tree views of the old numbering are dead
+        return st.as_dict(), old_to_new[:st.old_size]
+
     def tree_truncate(self, size):
         nat.check(nat.lib().lqrrt_tree_truncate(self.h, int(size)))
         self.epoch += 1

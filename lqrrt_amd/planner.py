@@ -163,6 +163,10 @@ class Planner:
         run = self._plan_begin(x0, sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time)
         if run is None:
             return False
+        return self._plan_loop(run)
+
+    def _plan_loop(self, run):
+        """The native calls of one plan (update_plan, replan) and its wrap-up."""
         # Each native call grows the tree by a few waves.  The clock and the kill flag are looked at between calls, so a
         # call is sized to what the time budget still allows.
         while True:
@@ -171,7 +175,7 @@ class Planner:
             # planner.py:293); before that, hits are bookkept by the engine (lqrrt_plan_best) and reported with the call.
             t_call = time.perf_counter()
             st = run.eng.extend(self.wave_size, max_attempts=budget, node_limit=int(self.max_nodes),
-                                pruning=pruning, stop_on_goal=bool(run.time_elapsed >= run.min_time))
+                                pruning=run.pruning, stop_on_goal=bool(run.time_elapsed >= run.min_time))
             if self._plan_after_call(run, st, time.perf_counter() - t_call):
                 break
         return self._plan_end(run)
@@ -190,7 +194,9 @@ class Planner:
 
     # The three phases of update_plan, separately callable so that several planners can share native calls (update_plans below):
     # set-up (planner.py:157-231), what follows each native call (:260-311 as far as the host is concerned), wrap-up (:313-336).
-    def _plan_begin(self, x0, sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time, seed=None):
+    def _plan_begin(self, x0, sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time, seed=None, retain=None):
+        """retain = (root, revalidate): the plan is seeded with node `root` of the tree this planner's engine holds (replan) --
+        tree_retain instead of tree_reset; x0 is then the root's state."""
         x0 = np.array(x0, dtype=np.float64)
         if self.goal is None:
             print("No goal has been set yet!")
@@ -242,7 +248,13 @@ class Planner:
                                adaptive=True, hspan_min=int(self.hspan[0]), horizon_iters_state=int(self.horizon_iters))
         else:
             eng.set_resolution(self.dt, self.FPR, self.horizon_iters, self.error_tol, self.goal, self.constraints.goal_buffer)
-        eng.tree_reset(x0)                                          # planner.py:172
+        if retain is None:
+            eng.tree_reset(x0)                                      # planner.py:172
+            self.retained = None
+        else:
+            self.retained, _ = eng.tree_retain(retain[0], revalidate=retain[1])
+            x0 = eng.states(0, 1)[0]
+        self._grown_with = self._tree_resolution()
         if not run.user_sampler:
             eng.set_sampler(np.mean(space, axis=1), np.diff(space).flatten(), bias, tries_limit)
             if run.own_stream:
@@ -264,7 +276,69 @@ class Planner:
         run.total = None
         run.rate = None                                             # attempts per second of real time, measured
         run.adopted = False
+        if retain is not None and self.retained["goal_hits"] > 0:
+            # a kept plan: _plan_after_call asks plan_best() only after a call with NEW hits, so the run starts with it
+            self.plan_reached_goal = True
+            self.T = self.retained["best_steps"] * self.dt
+            run.best_end = self.retained["best_end"]
         return run
+
+    def _tree_resolution(self):
+        """What the device tree's edges depend on and replan cannot change: dt and the layout of the edge pools."""
+        return (float(self.dt), int(self.hspan[1]) if self.hfactor else int(self.horizon_iters), bool(self.hfactor))
+
+    def replan(self, root, sample_space, goal_bias=0,
+               guide=None, xrand_gen=None, pruning=True,
+               finish_on_goal=False, specific_time=None, revalidate=True):
+        """
+        update_plan whose seed is node `root` of the tree the last plan left on this planner's engine -- typically a node of the
+        plan being driven, `planner.node_seq[k]` (see plan_node_after).  Not in the reference, which starts every plan from one
+        node (planner.py:172) and spends its budget finding the goal again.  The subtree below `root` is kept on the device,
+        goal hits included: with `revalidate` every kept edge is first tested against the world as it is NOW (the system's
+        obstacles / occupancy grid are synchronised first) and whatever hangs below a failing edge is dropped; the kept nodes are
+        renumbered (ascending), goal bookkeeping and ignore set are rebuilt against the current goal (csrc/retain.hpp; the rule:
+        tests/retain_reference.py).  Then the same loop, budget, kill and exit rules, wrap-up and return value as update_plan;
+        x_seq[0] is the root's state, the kept nodes count toward max_nodes, and a kept plan counts as found from the start.
+        `planner.retained` holds what was kept (old_size, kept, outside, infeasible, orphaned, root_feasible, goal_hits, best_end,
+        best_steps).  Node ids of the previous plan are void afterwards; a Tree object kept from it stays what it was.  A
+        finish_on_goal node lives on the host and is not part of the kept tree.
+
+        ValueError: `root` is not a node of the device tree.  RuntimeError: there is no tree to keep (no previous plan; system,
+        max_nodes, wave_size or device changed, which recreates the engine; dt or horizon differ from the ones the tree grew with).
+        NotImplementedError: callback mode.
+        """
+        self._resolve_mode()
+        if self.callback_mode:
+            raise NotImplementedError("replan: in callback mode the tree's gains and edges live in Python lists and feasibility is the "
+                                      "user's Python function, which the device cannot call; use update_plan.")
+        eng = self._engine
+        key = (id(self.system), int(self.max_nodes) + self.wave_size + 8, self.wave_size, self.device)
+        if eng is None or self._engine_key != key or getattr(self, "_grown_with", None) is None or eng.size < 1:
+            raise RuntimeError("replan: there is no tree to keep (no previous plan on this planner's engine, or system / max_nodes / "
+                               "wave_size / device changed since); use update_plan.")
+        if self._grown_with != self._tree_resolution():
+            raise RuntimeError("replan: dt or horizon differ from the ones the tree grew with; use update_plan.")
+        root = int(root)
+        if not 0 <= root < eng.size:
+            raise ValueError("The given parent ID, {}, doesn't exist.".format(root))       # tree.py:84
+        run = self._plan_begin(eng.states(root, 1)[0], sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time,
+                               retain=(root, bool(revalidate)))
+        if run is None:
+            return False
+        return self._plan_loop(run)
+
+    def plan_node_after(self, t):
+        """(k, node_id, t_k): the first node of the current plan that is reached at or after time `t` along it -- node_seq[k],
+        reached at t_k (the last node when t lies beyond the plan's end).  What a plan-drive-plan loop seeds the next plan with
+        (replan) where the reference's loop takes get_state(next_runtime).  Host only."""
+        if getattr(self, "node_seq", None) is None or self.tree is None:
+            raise RuntimeError("plan_node_after: there is no plan.")
+        steps = 0
+        for k, node in enumerate(self.node_seq):
+            steps += len(self.tree.x_seq[int(node)])
+            t_k = (steps - 1) * self.dt                             # the node's state is the last row of its edge
+            if t_k >= t or k == len(self.node_seq) - 1:
+                return k, int(node), t_k
 
     def _plan_budget(self, run):
         """Attempts the next native call may commit for this plan; a user sampling function is called for as many samples."""
