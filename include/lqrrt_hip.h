@@ -285,6 +285,20 @@ typedef struct {
 } lqrrt_retain_stats;
 int lqrrt_tree_retain(lqrrt_engine* e, int new_root, int revalidate, lqrrt_retain_stats* out, int32_t* old_to_new_host, void* stream);
 
+/* lqrrt_tree_retain for n engines at once (lqrrt_amd.update_plans jobs with a `root`: a fleet that replans every tick): engine i
+ * keeps the subtree below new_roots[i], revalidating when revalidate[i] != 0 (NULL: nobody revalidates), by the rule above -- every
+ * tree, out[i], old_to_new_host[i] [old size of engine i] (the array or single entries may be NULL) and every engine's host state
+ * are exactly what n calls of lqrrt_tree_retain give.  What is shared is the work around the kernels: every stage is ONE launch
+ * whose grid spans the engines, and allocations, waits and copies are per call, not per engine (DESIGN.md section 10 gives the
+ * transient scratch).  More than 32 engines run as consecutive chunks of up to 32 on `stream`.  Synchronous.
+ * The engines share the device, the model, the horizon and the form of S (as in lqrrt_engine_extend_multi; Riccati systems are
+ * welcome: a retain computes no gain), n <= 128, and no engine appears twice.  EVERY argument of EVERY engine is checked before
+ * anything is written, with lqrrt_tree_retain's codes and messages.  A failure before the first array of the first chunk is moved
+ * (arguments, allocation of the scratch) leaves all trees unchanged; after a later failure the trees of the call's engines are
+ * undefined, as after a failed lqrrt_engine_extend_multi: lqrrt_tree_reset or lqrrt_tree_load them before they are used again. */
+int lqrrt_tree_retain_multi(lqrrt_engine** engines, int n, const int32_t* new_roots, const int32_t* revalidate,
+                            lqrrt_retain_stats* out, int32_t** old_to_new_host, void* stream);
+
 /* Overwrites the ignore bits of nodes [first, first+count) (planner.py:270 `ignores`). */
 int lqrrt_tree_set_ignored(lqrrt_engine* e, int first, int count, const uint8_t* flags_host);
 

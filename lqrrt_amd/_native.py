@@ -91,6 +91,7 @@ SIGNATURES = {
     "lqrrt_tree_truncate": (_I, [_P, _I]),
     "lqrrt_tree_set_ignored": (_I, [_P, _I, _I, _P]),
     "lqrrt_tree_retain": (_I, [_P, _I, _I, C.POINTER(RetainStats), _P, _P]),
+    "lqrrt_tree_retain_multi": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "lqrrt_tree_get_edges": (_I, [_P, _I, _I, _P, _P]),
     "lqrrt_tree_mark": (_I, [_P]),
     "lqrrt_tree_rewind": (_I, [_P]),

@@ -15,6 +15,31 @@ struct RetainScratch {
     }
 };
 
+// Host state of an engine after a retain of its N-node tree, as lqrrt_tree_load / lqrrt_tree_truncate leave it, and the stats.
+// h: the counters; ign: the new ignore bitmap (kept / 64 + 1 words); h_npid / h_nelen: the new parents and edge lengths (kept
+// entries; not read when every node was kept).  The ignore words still have to be flushed.
+static void retain_adopt(lqrrt_engine* e, int N, const RetainOut& h, const std::vector<unsigned long long>& ign, std::vector<int>& h_npid,
+                         std::vector<int>& h_nelen, lqrrt_retain_stats* out) {
+    const int kept = h.kept;
+    if (kept < N) { e->h_pid.swap(h_npid); e->h_elen.swap(h_nelen); }
+    else e->h_elen[0] = 1;
+    std::fill(e->h_ign.begin(), e->h_ign.end(), 0ull);
+    std::copy(ign.begin(), ign.end(), e->h_ign.begin());
+    e->ign_hi = std::max(e->ign_hi, N);                         // the device words of the dropped nodes are cleared by the next upload
+    e->ign_dirty = true; e->ign_patch_valid = false;
+    e->N = kept;
+    e->werr_valid = false;
+    e->goal_hits = h.hits;
+    if (h.best != ~0ull) { e->best_end = (int)(h.best & 0xffffffffull); e->best_steps = (int64_t)(h.best >> 32); }
+    else { e->best_end = -1; e->best_steps = -1; }
+    e->mark_N = 0;
+    e->tot.tree_size = kept;
+    e->ctl_w = 0.0;
+    e->proto_cache.clear();                                      // (multi-engine path: the prototype is uploaded again)
+    out->old_size = N; out->kept = kept; out->outside = h.outside; out->infeasible = h.infeasible; out->orphaned = h.orphaned;
+    out->root_feasible = h.root_feasible; out->goal_hits = h.hits; out->best_end = e->best_end; out->best_steps = e->best_steps;
+}
+
 static int retain_run(lqrrt_engine* e, int root, int revalidate, lqrrt_retain_stats* out, int32_t* old_to_new, hipStream_t st,
                       RetainScratch& sc) {
     const int N = e->N, n = e->n, m = e->m, H = e->H;
@@ -132,27 +157,9 @@ static int retain_run(lqrrt_engine* e, int root, int revalidate, lqrrt_retain_st
     if (old_to_new) HIPCHK(hipMemcpyAsync(old_to_new, d_newid, sizeof(int) * N, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
 
-    // ---- host state, as lqrrt_tree_load / lqrrt_tree_truncate leave it
-    if (kept < N) { e->h_pid.swap(h_npid); e->h_elen.swap(h_nelen); }
-    else e->h_elen[0] = 1;
-    std::fill(e->h_ign.begin(), e->h_ign.end(), 0ull);
-    std::copy(ign.begin(), ign.end(), e->h_ign.begin());
-    e->ign_hi = std::max(e->ign_hi, N);                         // the device words of the dropped nodes are cleared by the next upload
-    e->ign_dirty = true; e->ign_patch_valid = false;
-    e->N = kept;
-    e->werr_valid = false;
-    e->goal_hits = h.hits;
-    if (h.best != ~0ull) { e->best_end = (int)(h.best & 0xffffffffull); e->best_steps = (int64_t)(h.best >> 32); }
-    else { e->best_end = -1; e->best_steps = -1; }
-    e->mark_N = 0;
-    e->tot.tree_size = kept;
-    e->ctl_w = 0.0;
-    e->proto_cache.clear();                                      // (multi-engine path: the prototype is uploaded again)
+    retain_adopt(e, N, h, ign, h_npid, h_nelen, out);
     TRY(flush_ignore(e, st, false));
     HIPCHK(hipStreamSynchronize(st));
-
-    out->old_size = N; out->kept = kept; out->outside = h.outside; out->infeasible = h.infeasible; out->orphaned = h.orphaned;
-    out->root_feasible = h.root_feasible; out->goal_hits = h.hits; out->best_end = e->best_end; out->best_steps = e->best_steps;
     return 0;
 }
 
@@ -168,4 +175,272 @@ extern "C" int lqrrt_tree_retain(lqrrt_engine* e, int new_root, int revalidate, 
     HIPCHK(hipStreamSynchronize(st));                           // nothing of the old tree may still be in flight
     RetainScratch sc;
     return retain_run(e, new_root, revalidate ? 1 : 0, out, old_to_new_host, st, sc);
+}
+
+// --------------------------------------------------------------------------------------------
+// Several trees per call: lqrrt_tree_retain_multi (update_plans jobs with a `root`).  The stages of retain_run, each as ONE launch
+// whose grid spans the engines of a chunk (retain.hpp k_retain_*_multi), and per CHUNK -- not per engine -- two allocations, two
+// waits for the stream before the final one, and a handful of copies: the per-engine arrays of one kind lie back to back in one
+// small scratch, so the counters, the ignore bitmaps, the id maps and the new parents / edge lengths each come back in one copy.
+//   small  as retain_run's, summed over the chunk's engines (~54 bytes per old node) + a RetainDesc per engine
+//   big    the kept rows of ONE pool at a time for every engine of the chunk that moves anything: 8 * widest * (sum of their kept)
+//          bytes, widest = max(H n, H m, m n) doubles per node -- for 16 boat_advanced trees that keep 5000 nodes each 77 MB
+// Both are freed before the call returns and are not part of any engine's footprint.
+struct RetainMultiScratch {
+    char* small = nullptr;
+    double* big = nullptr;
+    ~RetainMultiScratch() {
+        if (small) (void)hipFree(small);
+        if (big) (void)hipFree(big);
+    }
+};
+
+// prefix table of a launch from the workgroups every engine takes; returns the grid size
+static unsigned retain_grid(const std::vector<long long>& counts, RetainGrid& gr) {
+    memset(&gr, 0, sizeof gr);
+    const int n = (int)counts.size();
+    long long at = 0;
+    gr.n = n;
+    for (int i = 0; i < n; ++i) { gr.block0[i] = (int)at; at += counts[i]; }
+    gr.block0[n] = gr.block0[n + 1] = (int)at;
+    return (unsigned)at;
+}
+
+constexpr long long RETAIN_MULTI_NODES = 1ll << 25;             // old nodes per chunk: a wavefront per node stays below 2^32 threads per launch
+
+static int retain_multi_chunk(lqrrt_engine** eng, int n, const int32_t* roots, const int32_t* reval, lqrrt_retain_stats* out,
+                              int32_t** old_to_new, hipStream_t st) {
+    lqrrt_engine* e0 = eng[0];
+    const int ns = e0->n, m = e0->m, H = e0->H, nw = e0->nw;
+    ProtoTable pt;
+    memset(&pt, 0, sizeof pt);
+    size_t lds = 0;
+    std::vector<size_t> offN((size_t)n + 1, 0), offB((size_t)n + 1, 0), offW((size_t)n + 1, 0);
+    int maxN = 1;
+    for (int i = 0; i < n; ++i) {
+        lqrrt_engine* e = eng[i];
+        TRY(multi_sync_proto(e, st));                           // (P, g, r, tv as they are now: a new map has been set before the call)
+        pt.p[i] = e->d_proto;
+        lds = std::max(lds, geo_lds_bytes(e));
+        offN[i + 1] = offN[i] + (size_t)e->N;
+        offB[i + 1] = offB[i] + (size_t)((e->N + RETAIN_BLOCK - 1) / RETAIN_BLOCK);
+        offW[i + 1] = offW[i] + ((size_t)e->cap / 64 + 1);
+        maxN = std::max(maxN, e->N);
+    }
+    const size_t sumN = offN[n], sumB = offB[n], sumW = offW[n];
+    // ---- small scratch: one allocation, one array per kind, the engines' slices back to back in it
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    const size_t o_a = carve(sizeof(RetainLink) * sumN), o_b = carve(sizeof(RetainLink) * sumN), o_ok = carve(sumN), o_keep = carve(sumN);
+    const size_t o_local = carve(sizeof(int) * sumN), o_sums = carve(sizeof(int) * sumB), o_newid = carve(sizeof(int) * sumN);
+    const size_t o_nelen = carve(sizeof(int) * sumN), o_npid = carve(sizeof(int) * sumN), o_nsteps = carve(sizeof(int) * sumN);
+    const size_t o_ign = carve(sizeof(unsigned long long) * sumW), o_out = carve(sizeof(RetainOut) * n), o_desc = carve(sizeof(RetainDesc) * n);
+    RetainMultiScratch sc;
+    const size_t keep_bytes = g_dalloc_bytes;
+    int rc = dalloc(&sc.small, off);
+    g_dalloc_bytes = keep_bytes;                                // (transient: not part of any engine's footprint)
+    if (rc) return rc;
+    RetainOut* d_out = (RetainOut*)(sc.small + o_out);
+    RetainDesc* d_desc = (RetainDesc*)(sc.small + o_desc);
+    int* d_newid = (int*)(sc.small + o_newid);
+    int* d_npid = (int*)(sc.small + o_npid);
+    int* d_nelen = (int*)(sc.small + o_nelen);
+    unsigned long long* d_ign = (unsigned long long*)(sc.small + o_ign);
+
+    std::vector<RetainDesc> hd((size_t)n);
+    std::vector<RetainOut> ho((size_t)n);
+    std::vector<long long> c_check((size_t)n), c_node((size_t)n), c_one((size_t)n, 1);
+    for (int i = 0; i < n; ++i) {
+        lqrrt_engine* e = eng[i];
+        RetainDesc& d = hd[i];
+        memset(&d, 0, sizeof d);
+        d.link[0] = (RetainLink*)(sc.small + o_a) + offN[i];
+        d.link[1] = (RetainLink*)(sc.small + o_b) + offN[i];
+        d.ok = (unsigned char*)(sc.small + o_ok) + offN[i];
+        d.keep = (unsigned char*)(sc.small + o_keep) + offN[i];
+        d.local = (int*)(sc.small + o_local) + offN[i];
+        d.sums = (int*)(sc.small + o_sums) + offB[i];
+        d.newid = d_newid + offN[i];
+        d.nelen = d_nelen + offN[i];
+        d.npid = d_npid + offN[i];
+        d.nsteps = (int*)(sc.small + o_nsteps) + offN[i];
+        d.ign = d_ign + offW[i];
+        d.out = d_out + i;
+        d.root = roots[i]; d.N = e->N; d.revalidate = reval && reval[i] ? 1 : 0;
+        d.nblocks = (int)(offB[i + 1] - offB[i]);
+        memset(&ho[i], 0, sizeof(RetainOut));
+        ho[i].best = ~0ull;
+        ho[i].root_feasible = 1;
+        c_check[i] = d.revalidate ? (long long)(e->N - roots[i]) : 0;
+        c_node[i] = d.nblocks;
+    }
+    HIPCHK(hipMemcpyAsync(d_out, ho.data(), sizeof(RetainOut) * n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_desc, hd.data(), sizeof(RetainDesc) * n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_ign, 0, sizeof(unsigned long long) * sumW, st));
+    const dim3 t256(RETAIN_BLOCK), t64(64);
+    RetainGrid g_check, g_node, g_one;
+    const unsigned n_check = retain_grid(c_check, g_check), n_node = retain_grid(c_node, g_node);
+    (void)retain_grid(c_one, g_one);
+
+    // ---- check (the engines that revalidate), with the largest LDS image of the call's geometries
+    if (n_check > 0) {
+        DISPATCH(e0, hipLaunchKernelGGL((k_retain_check_multi<S>), dim3(n_check), t64, lds, st, pt, (const RetainDesc*)d_desc, g_check));
+        HIPCHK(hipGetLastError());
+    }
+    // ---- propagate: 2^rounds >= the LARGEST tree of the chunk (retain.hpp: the extra rounds are the identity on a smaller one)
+    hipLaunchKernelGGL(k_retain_init_multi, dim3(n_node), t256, 0, st, pt, (const RetainDesc*)d_desc, g_node);
+    int rounds = 0;
+    while ((1ll << rounds) < (long long)maxN) ++rounds;
+    for (int r = 0; r < rounds; ++r)
+        hipLaunchKernelGGL(k_retain_double_multi, dim3(n_node), t256, 0, st, pt, (const RetainDesc*)d_desc, g_node, r & 1);
+    const int fin = rounds & 1;
+    // ---- scan
+    hipLaunchKernelGGL(k_retain_flags_multi, dim3(n_node), t256, 0, st, pt, (const RetainDesc*)d_desc, g_node, fin);
+    hipLaunchKernelGGL(k_retain_scan_sums_multi, dim3((unsigned)n), t256, 0, st, (const RetainDesc*)d_desc, n);
+    hipLaunchKernelGGL(k_retain_ids_multi, dim3(n_node), t256, 0, st, pt, (const RetainDesc*)d_desc, g_node, fin);
+    hipLaunchKernelGGL(k_retain_parents_multi, dim3(n_node), t256, 0, st, pt, (const RetainDesc*)d_desc, g_node);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ho.data(), d_out, sizeof(RetainOut) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    size_t sum_kept = 0;
+    bool any_moves = false;
+    for (int i = 0; i < n; ++i) {
+        const int kept = ho[i].kept;
+        if (kept < 1 || kept > eng[i]->N) return fail(LQRRT_E_HIP, "retain: the scan counted %d kept nodes of %d (engine %d)", kept, eng[i]->N, i);
+        if (kept < eng[i]->N) { sum_kept += (size_t)kept; any_moves = true; }
+    }
+
+    // ---- move (nothing of any tree has been written so far).  An engine that keeps every node moves nothing.
+    const size_t widest = std::max(std::max((size_t)H * std::max(ns, m), (size_t)m * ns), (size_t)std::max(ns, 2 * nw));
+    if (any_moves) {
+        rc = dalloc(&sc.big, sum_kept * widest);
+        g_dalloc_bytes = keep_bytes;
+        if (rc) return rc;
+    }
+    std::vector<RetainDesc> hd2(hd);                           // (a second staging copy: the first upload may still read `hd`)
+    std::vector<long long> c_old((size_t)n), c_oldb((size_t)n), c_new((size_t)n), c_newb((size_t)n), c_small((size_t)n), c_goal((size_t)n);
+    {
+        size_t at = 0;
+        for (int i = 0; i < n; ++i) {
+            lqrrt_engine* e = eng[i];
+            const int kept = ho[i].kept;
+            const bool mv = kept < e->N;
+            hd2[i].moves = mv ? 1 : 0;
+            hd2[i].big = mv ? sc.big + at * widest : nullptr;
+            hd2[i].has_goal = (e->has_goal && kept > 1) ? 1 : 0;
+            if (mv) at += (size_t)kept;
+            c_old[i] = mv ? e->N : 0;
+            c_oldb[i] = mv ? hd2[i].nblocks : 0;
+            c_new[i] = mv ? kept : 0;
+            c_newb[i] = mv ? (kept + RETAIN_BLOCK - 1) / RETAIN_BLOCK : 0;
+            c_small[i] = mv ? c_newb[i] : 1;
+            c_goal[i] = hd2[i].has_goal ? (kept - 1 + RETAIN_BLOCK - 1) / RETAIN_BLOCK : 0;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(d_desc, hd2.data(), sizeof(RetainDesc) * n, hipMemcpyHostToDevice, st));
+    RetainGrid g_old, g_oldb, g_new, g_newb, g_small, g_goal;
+    const unsigned n_old = retain_grid(c_old, g_old), n_oldb = retain_grid(c_oldb, g_oldb), n_new = retain_grid(c_new, g_new);
+    const unsigned n_newb = retain_grid(c_newb, g_newb), n_small = retain_grid(c_small, g_small), n_goal = retain_grid(c_goal, g_goal);
+    if (any_moves) {
+        // SoA tables: all components of a table through the scratch at once
+        for (int which = 0; which < 2; ++which) {
+            const int rows = which == 0 ? ns : 2 * nw;
+            if (rows < 1) continue;
+            hipLaunchKernelGGL(k_retain_gather1_multi, dim3(n_oldb, (unsigned)rows), t256, 0, st, pt, (const RetainDesc*)d_desc, g_oldb, which);
+            hipLaunchKernelGGL(k_retain_scatter1_multi, dim3(n_newb, (unsigned)rows), t256, 0, st, pt, (const RetainDesc*)d_desc, g_newb, which);
+        }
+        // AoS pools: K whole, the edges row by recorded row (the gathers read the OLD edge lengths: tv.elen is replaced last)
+        const int pw[3] = {m * ns, H * ns, H * m}, pper[3] = {0, ns, m};
+        for (int which = 0; which < 3; ++which) {
+            hipLaunchKernelGGL(k_retain_gather_multi, dim3(n_old), t64, 0, st, pt, (const RetainDesc*)d_desc, g_old, which, pw[which], pper[which]);
+            hipLaunchKernelGGL(k_retain_scatter_multi, dim3(n_new), t64, 0, st, pt, (const RetainDesc*)d_desc, g_new, which, pw[which], pper[which]);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_retain_small_multi, dim3(n_small), t256, 0, st, pt, (const RetainDesc*)d_desc, g_small);
+    hipLaunchKernelGGL(k_retain_root_edge_multi, dim3((unsigned)n), t64, 0, st, pt, n, ns, m);
+    HIPCHK(hipGetLastError());
+    // ---- goal (on the new trees)
+    if (n_goal > 0) {
+        DISPATCH(e0, hipLaunchKernelGGL((k_retain_goal_multi<S>), dim3(n_goal), t256, 0, st, pt, (const RetainDesc*)d_desc, g_goal));
+        HIPCHK(hipGetLastError());
+    }
+    // ---- back to the host: one copy per kind for the whole chunk
+    std::vector<unsigned long long> h_ign(sumW);
+    std::vector<int> h_newid, h_npid_all, h_nelen_all;
+    bool want_map = false;
+    if (old_to_new)
+        for (int i = 0; i < n; ++i) want_map = want_map || old_to_new[i] != nullptr;
+    HIPCHK(hipMemcpyAsync(ho.data(), d_out, sizeof(RetainOut) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_ign.data(), d_ign, sizeof(unsigned long long) * sumW, hipMemcpyDeviceToHost, st));
+    if (want_map) {
+        h_newid.resize(sumN);
+        HIPCHK(hipMemcpyAsync(h_newid.data(), d_newid, sizeof(int) * sumN, hipMemcpyDeviceToHost, st));
+    }
+    if (any_moves) {
+        h_npid_all.resize(sumN); h_nelen_all.resize(sumN);
+        HIPCHK(hipMemcpyAsync(h_npid_all.data(), d_npid, sizeof(int) * sumN, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_nelen_all.data(), d_nelen, sizeof(int) * sumN, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+
+    // ---- host state of every engine, as retain_run leaves it
+    for (int i = 0; i < n; ++i) {
+        lqrrt_engine* e = eng[i];
+        const int N = e->N, kept = ho[i].kept;
+        std::vector<int> h_npid, h_nelen;
+        if (kept < N) {
+            h_npid.assign(h_npid_all.begin() + (ptrdiff_t)offN[i], h_npid_all.begin() + (ptrdiff_t)offN[i] + kept);
+            h_nelen.assign(h_nelen_all.begin() + (ptrdiff_t)offN[i], h_nelen_all.begin() + (ptrdiff_t)offN[i] + kept);
+        }
+        const std::vector<unsigned long long> ign(h_ign.begin() + (ptrdiff_t)offW[i], h_ign.begin() + (ptrdiff_t)offW[i] + (kept / 64 + 1));
+        if (old_to_new && old_to_new[i]) memcpy(old_to_new[i], h_newid.data() + offN[i], sizeof(int) * (size_t)N);
+        retain_adopt(e, N, ho[i], ign, h_npid, h_nelen, &out[i]);
+        TRY(flush_ignore(e, st, false));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int lqrrt_tree_retain_multi(lqrrt_engine** engines, int n, const int32_t* new_roots, const int32_t* revalidate,
+                                       lqrrt_retain_stats* out, int32_t** old_to_new_host, void* stream) {
+    if (!engines || n < 1) return fail(LQRRT_E_ARG, "no engines");
+    if (!new_roots || !out) return fail(LQRRT_E_ARG, "null argument");
+    if (n > 4 * MULTI_MAX) return fail(LQRRT_E_ARG, "at most %d engines per call", 4 * (int)MULTI_MAX);
+    lqrrt_engine* e0 = engines[0];
+    // every argument of every engine, before anything is written
+    for (int i = 0; i < n; ++i) {
+        lqrrt_engine* e = engines[i];
+        if (!e) return fail(LQRRT_E_ARG, "null engine");
+        NOT_GENERIC(e);
+        for (int j = 0; j < i; ++j)
+            if (engines[j] == e) return fail(LQRRT_E_ARG, "engine %d appears twice", i);
+        if (e->device != e0->device || e->model != e0->model || e->H != e0->H || (e->d_S != nullptr) != (e0->d_S != nullptr))
+            return fail(LQRRT_E_ARG, "engines of one call share the device, the model, the horizon and the form of S");
+        if (!e->has_res || e->N < 1) return fail(LQRRT_E_STATE, "no tree to retain: set_resolution and tree_reset / tree_load first");
+        if (new_roots[i] < 0 || new_roots[i] >= e->N) return fail(LQRRT_E_ARG, "The given parent ID, %d, doesn't exist.", new_roots[i]);   // tree.py:83-84
+        if ((long long)e->N * e->H > 0x7fffffffLL) return fail(LQRRT_E_ARG, "tree too large for 32-bit step counts");
+    }
+    TRY(use_device(e0));
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(st));                           // nothing of the old trees may still be in flight
+    // chunks of up to MULTI_MAX engines (the pointer table of a launch), one after the other on the same stream
+    for (int first = 0; first < n;) {
+        int count = 0;
+        long long nodes = 0;
+        while (first + count < n && count < MULTI_MAX && (count == 0 || nodes + engines[first + count]->N <= RETAIN_MULTI_NODES)) {
+            nodes += engines[first + count]->N;
+            ++count;
+        }
+        const int rc = retain_multi_chunk(engines + first, count, new_roots + first, revalidate ? revalidate + first : nullptr, out + first,
+                                          old_to_new_host ? old_to_new_host + first : nullptr, st);
+        if (rc) {
+            const std::string keep = g_err;
+            (void)hipStreamSynchronize(st);                     // nothing in flight when the scratch goes
+            g_err = keep;
+            return rc;
+        }
+        first += count;
+    }
+    return 0;
 }

@@ -200,6 +200,39 @@ class Engine(object):
         self.generation += 1          # bound Tree views of the old numbering are dead
         return st.as_dict(), old_to_new[:st.old_size]
 
+    @staticmethod
+    def tree_retain_multi(engines, roots, revalidate=True):
+        """lqrrt_tree_retain_multi: tree_retain for n engines in one native call -- every stage one kernel launch that spans the
+        engines, allocations and waits per call instead of per engine.  `roots`: one node id per engine; `revalidate`: one flag for
+        all or one per engine.  Returns [(stats dict, old_to_new)] in the engines' order, each exactly what that engine's own
+        tree_retain(root, revalidate) returns.  The engines share device, model, horizon and form of S.  Every argument is checked
+        before any tree is touched (ValueError / NativeError as tree_retain); after a failure past that point the trees of all
+        engines of the call are undefined."""
+        engines = list(engines)
+        n = len(engines)
+        if n < 1:
+            raise ValueError("no engines")
+        roots = np.ascontiguousarray([int(r) for r in roots], dtype=np.int32)
+        if roots.shape != (n,):
+            raise ValueError("expected one root per engine")
+        flags = np.ascontiguousarray(np.broadcast_to(np.asarray(revalidate, dtype=bool), (n,)), dtype=np.int32)
+        handles = (C.c_void_p * n)(*[e.h for e in engines])
+        stats = (nat.RetainStats * n)()
+        maps = [np.empty(max(e.size, 1), dtype=np.int32) for e in engines]
+        map_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in maps])
+        try:
+            nat.check(nat.lib().lqrrt_tree_retain_multi(handles, n, nat.ptr(roots), nat.ptr(flags), stats, map_ptrs,
+                                                        engines[0]._stream()))
+        except ValueError:
+            raise                         # (bad arguments are refused before anything is written: trees and views stand)
+        except Exception:
+            for e in engines:
+                e.generation += 1         # (whatever the trees are now, views of the old ones are dead)
+            raise
+        for e in engines:
+            e.generation += 1             # bound Tree views of the old numbering are dead
+        return [(stats[i].as_dict(), maps[i][:stats[i].old_size]) for i in range(n)]
+
     def tree_truncate(self, size):
         nat.check(nat.lib().lqrrt_tree_truncate(self.h, int(size)))
         self.epoch += 1

@@ -196,7 +196,19 @@ class Planner:
     # set-up (planner.py:157-231), what follows each native call (:260-311 as far as the host is concerned), wrap-up (:313-336).
     def _plan_begin(self, x0, sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time, seed=None, retain=None):
         """retain = (root, revalidate): the plan is seeded with node `root` of the tree this planner's engine holds (replan) --
-        tree_retain instead of tree_reset; x0 is then the root's state."""
+        tree_retain instead of tree_reset; x0 is then the root's state.  Three steps, separately callable so that the planners of
+        an update_plans group can share the middle one (one tree_retain_multi for all of them)."""
+        run = self._plan_prepare(x0, sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time, seed)
+        if run is None:
+            return None
+        if retain is None:
+            run.eng.tree_reset(run.x0)                              # planner.py:172
+            return self._plan_start(run, None)
+        return self._plan_start(run, run.eng.tree_retain(retain[0], revalidate=retain[1])[0])
+
+    def _plan_prepare(self, x0, sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time, seed=None):
+        """First step of _plan_begin, this planner alone: arguments, the old Tree object retired, geometry synchronised, sample
+        stream and resolution set.  The device tree is as the last plan left it."""
         x0 = np.array(x0, dtype=np.float64)
         if self.goal is None:
             print("No goal has been set yet!")
@@ -248,14 +260,21 @@ class Planner:
                                adaptive=True, hspan_min=int(self.hspan[0]), horizon_iters_state=int(self.horizon_iters))
         else:
             eng.set_resolution(self.dt, self.FPR, self.horizon_iters, self.error_tol, self.goal, self.constraints.goal_buffer)
-        if retain is None:
-            eng.tree_reset(x0)                                      # planner.py:172
-            self.retained = None
-        else:
-            self.retained, _ = eng.tree_retain(retain[0], revalidate=retain[1])
+        run.x0, run.seed = x0, seed
+        if not run.user_sampler:
+            run.sampler = (space, bias, tries_limit)
+        return run
+
+    def _plan_start(self, run, retained):
+        """Last step of _plan_begin, after the engine's tree was reset (retained = None) or retained (its stats): sampler, the new
+        Tree bound to the device tree, the run's clock; a kept plan counts as found from the start."""
+        eng, x0, seed = run.eng, run.x0, run.seed
+        self.retained = retained
+        if retained is not None:
             x0 = eng.states(0, 1)[0]
         self._grown_with = self._tree_resolution()
         if not run.user_sampler:
+            space, bias, tries_limit = run.sampler
             eng.set_sampler(np.mean(space, axis=1), np.diff(space).flatten(), bias, tries_limit)
             if run.own_stream:
                 st = np.random.RandomState(seed).get_state()
@@ -276,7 +295,7 @@ class Planner:
         run.total = None
         run.rate = None                                             # attempts per second of real time, measured
         run.adopted = False
-        if retain is not None and self.retained["goal_hits"] > 0:
+        if retained is not None and retained["goal_hits"] > 0:
             # a kept plan: _plan_after_call asks plan_best() only after a call with NEW hits, so the run starts with it
             self.plan_reached_goal = True
             self.T = self.retained["best_steps"] * self.dt
@@ -311,6 +330,16 @@ class Planner:
         if self.callback_mode:
             raise NotImplementedError("replan: in callback mode the tree's gains and edges live in Python lists and feasibility is the "
                                       "user's Python function, which the device cannot call; use update_plan.")
+        root = self._replan_check(root)
+        eng = self._engine
+        run = self._plan_begin(eng.states(root, 1)[0], sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time,
+                               retain=(root, bool(revalidate)))
+        if run is None:
+            return False
+        return self._plan_loop(run)
+
+    def _replan_check(self, root):
+        """What replan refuses (update_plans checks it for every job with a `root` before it touches a planner); returns int(root)."""
         eng = self._engine
         key = (id(self.system), int(self.max_nodes) + self.wave_size + 8, self.wave_size, self.device)
         if eng is None or self._engine_key != key or getattr(self, "_grown_with", None) is None or eng.size < 1:
@@ -321,11 +350,7 @@ class Planner:
         root = int(root)
         if not 0 <= root < eng.size:
             raise ValueError("The given parent ID, {}, doesn't exist.".format(root))       # tree.py:84
-        run = self._plan_begin(eng.states(root, 1)[0], sample_space, goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time,
-                               retain=(root, bool(revalidate)))
-        if run is None:
-            return False
-        return self._plan_loop(run)
+        return root
 
     def plan_node_after(self, t):
         """(k, node_id, t_k): the first node of the current plan that is reached at or after time `t` along it -- node_seq[k],
@@ -666,6 +691,13 @@ def update_plans(jobs):
     """
     Several planners plan at once: `jobs` is a list of dicts, each with the keys `planner`, `x0`, `sample_space` and, optionally,
     update_plan's keyword arguments (goal_bias, guide, xrand_gen, pruning, finish_on_goal, specific_time) plus `seed` and `group`.
+    A job that gives `root` INSTEAD of `x0` is that planner's replan(root, ...): the subtree below node `root` of the tree its last
+    plan left on the device is kept, with `revalidate` (default True) against the world as it is now, and the plan is seeded with it
+    -- a fleet in a plan-drive-plan loop replans every vehicle every tick without searching for the goal again.  The kept trees of a
+    group come from ONE batched native call (lqrrt_tree_retain_multi, csrc/retain.hpp: every stage of the retain one launch for all
+    trees), the jobs with `x0` of the same call reset theirs; both kinds may be mixed.  Per planner the result -- `retained`, tree,
+    plan -- is that of np.random.seed(seed); planner.replan(root, ...).  Whatever replan refuses (no tree to keep, dt or horizon
+    changed: RuntimeError; a root that does not exist: ValueError; replan's messages) is refused here too.
     Every planner gets exactly what its own update_plan would give it -- its tree is the one it grows alone from the same sample
     stream -- but the native calls are shared: lqrrt_engine_extend_multi advances all trees of a GROUP in lock step with two kernel
     launches per tick whatever their number (csrc/engine_multi.hpp), which is how one MI355X is filled by planners that each use ~2 %
@@ -685,10 +717,12 @@ def update_plans(jobs):
     a call is sized by the smallest remaining budget of the group and the wrap-up of finished plans is deferred until the group's
     loop has ended, so a planner overruns its max_time by at most one shared call (the same bound as a solo update_plan) whatever
     the number of jobs.  A goal hit of ANY planner ends the running call early once some planner of the group is past its min_time
-    (the others just continue with the next call).  Returns the list of update_plan's return values.  Not in the reference: its
-    Planner plans one tree on one core.
+    (the others just continue with the next call).  Set-up -- per planner, then the group's batched retain, then per planner again --
+    happens before the groups' loops start, outside every planner's clock.  If the batched retain fails, the trees of that group's
+    planners are unreadable and their next plan builds a fresh engine, as after a failed shared extend call.  Returns the list of
+    update_plan's return values.  Not in the reference: its Planner plans one tree on one core.
     """
-    keys = ("goal_bias", "guide", "xrand_gen", "pruning", "finish_on_goal", "specific_time", "seed", "group")
+    keys = ("goal_bias", "guide", "xrand_gen", "pruning", "finish_on_goal", "specific_time", "seed", "group", "revalidate")
     jobs = [dict(j) for j in jobs]
     if not jobs:
         return []
@@ -697,11 +731,13 @@ def update_plans(jobs):
         raise ValueError("update_plans: a planner appears twice.")
     groups = {}
     for k, (p, j) in enumerate(zip(planners, jobs)):
-        unknown = set(j) - set(keys) - {"planner", "x0", "sample_space"}
+        unknown = set(j) - set(keys) - {"planner", "x0", "root", "sample_space"}
         if unknown:
             raise ValueError("update_plans: unknown job key(s) %s." % sorted(unknown))
-        if not isinstance(p, Planner) or "x0" not in j or "sample_space" not in j:
-            raise ValueError("update_plans: every job needs a planner, x0 and sample_space.")
+        if not isinstance(p, Planner) or ("x0" in j) == ("root" in j) or "sample_space" not in j:
+            raise ValueError("update_plans: every job needs a planner, sample_space and exactly one of x0 and root.")
+        if "revalidate" in j and "root" not in j:
+            raise ValueError("update_plans: `revalidate` belongs to a job with a `root`.")
         p._resolve_mode()
         if p.callback_mode:
             raise ValueError("update_plans: planners whose plugins are Python callables plan one by one (update_plan).")
@@ -729,19 +765,49 @@ def update_plans(jobs):
                     and bool(j.get("pruning", True)) == prun0)
             if not same:
                 raise ValueError("update_plans: the planners of a group must share system type, horizon, max_nodes, wave_size, pruning and device.")
+    # what replan refuses, with its messages, for every job with a root
+    for p, j in zip(planners, jobs):
+        if "root" in j:
+            j["root"] = p._replan_check(j["root"])
     unseeded = [k for k, j in enumerate(jobs) if j.get("seed") is None and (j.get("xrand_gen") is None or type(j.get("xrand_gen")) is int)]
     if len(unseeded) > 1 and any(getattr(planners[k], "printing", False) for k in unseeded):
         print("update_plans: %d planners use the default sampler without a `seed`: they all start from np.random's current state." % len(unseeded))
 
+    # Set-up in three steps (Planner._plan_begin's), so that every group does ONE batched retain: each planner alone, the group's
+    # trees (tree_retain_multi over the jobs with a root, tree_reset for the others), each planner alone again.
     results = [None] * len(jobs)
     runs = {}
     for k, (p, j) in enumerate(zip(planners, jobs)):
-        run = p._plan_begin(j["x0"], j["sample_space"], j.get("goal_bias", 0), j.get("guide"), j.get("xrand_gen"),
-                            bool(j.get("pruning", True)), j.get("finish_on_goal", False), j.get("specific_time"), seed=j.get("seed"))
+        x0 = p._engine.states(j["root"], 1)[0] if "root" in j else j["x0"]
+        run = p._plan_prepare(x0, j["sample_space"], j.get("goal_bias", 0), j.get("guide"), j.get("xrand_gen"),
+                              bool(j.get("pruning", True)), j.get("finish_on_goal", False), j.get("specific_time"), seed=j.get("seed"))
         if run is None:
             results[k] = False
         else:
             runs[k] = run
+    for g in sorted(groups, key=lambda g: min(groups[g])):
+        members = [k for k in groups[g] if k in runs]
+        rooted = [k for k in members if "root" in jobs[k]]
+        kept = {}
+        try:
+            if rooted:
+                done = Engine.tree_retain_multi([runs[k].eng for k in rooted], [jobs[k]["root"] for k in rooted],
+                                                [bool(jobs[k].get("revalidate", True)) for k in rooted])
+                kept = {k: stats for k, (stats, _) in zip(rooted, done)}
+            for k in members:
+                if k not in kept:
+                    runs[k].eng.tree_reset(runs[k].x0)              # planner.py:172
+        except Exception:
+            # as in group_loop below: nothing of these device trees may be read, the next plan builds a fresh engine.  (A Tree
+            # object of the plan before was detached in the first step: it is a host copy and stays what it was.)
+            for k in members:
+                tree = planners[k].tree
+                if tree is not None and tree.on_device:
+                    tree._e, tree._snap = None, None
+                planners[k]._engine_key = None
+            raise
+        for k in members:
+            planners[k]._plan_start(runs[k], kept.get(k))
 
     def group_loop(members):
         mine = [(k, planners[k], runs[k]) for k in members if k in runs]

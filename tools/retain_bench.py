@@ -10,6 +10,12 @@ more obstacle beside the best plan), so a revalidating retain has something to f
 
 The share of the check stage comes from a run of its own:
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/retain_bench.py --cases boat_1e5 --reps 1 --no-host
+
+Fleets (lqrrt_tree_retain_multi, update_plans jobs with a `root`): n boat_advanced trees of `--fleet-nodes` nodes from n seeds, each
+with its root a fifth of the way down its best plan and one more obstacle, revalidating -- ONE Engine.tree_retain_multi call next to
+the loop of Engine.tree_retain calls over identically grown twins, same process, warmed, median of `--reps`:
+    python tools/retain_bench.py --fleet 4,16,64,16x100000 [--fleet-nodes 10000] [--reps 3] [--out DIR]
+        ->  one JSON line per fleet size; --out DIR also writes DIR/retain_multi_bench.jsonl
 """
 import argparse
 import json
@@ -112,13 +118,85 @@ def run(case, reps, host):
     return out
 
 
+def run_fleet(n, nodes, reps):
+    """n trees through one tree_retain_multi call / n twins through tree_retain one after the other."""
+    fleet, twins, saved, roots = [], [], [], []
+    for k in range(n):
+        pair = []
+        for _ in range(2):
+            s = lqrrt_amd.systems.BoatAdvanced(0)
+            kw = s.plan_kwargs
+            eng = Engine(s, capacity=nodes + 2048, max_wave=1024)
+            eng.set_resolution(kw["dt"], kw["FPR"], int(kw["horizon"] / kw["dt"]), np.abs(s.error_tol), s.goal, np.abs(s.goal_buffer))
+            space = np.array(s.sample_space, dtype=np.float64)
+            eng.set_sampler(np.mean(space, axis=1), np.diff(space).flatten(), np.array(s.goal_bias, dtype=np.float64), 10)
+            st = np.random.RandomState(1 + k).get_state()
+            eng.set_mt19937(st[1], st[2])
+            eng.tree_reset(s.x0)
+            eng.extend(1024, node_limit=nodes - 1)
+            pair.append((s, eng))
+        (s, eng), (s2, twin) = pair
+        end = eng.plan_best()[0]
+        plan = eng.climb(end if end >= 0 else eng.size - 1)
+        roots.append(int(plan[max(1, len(plan) // 5)]) if len(plan) > 1 else 0)
+        change_world(s, eng, plan)
+        change_world(s2, twin, plan)
+        arr = rr.engine_arrays(eng)
+        live = np.arange(arr[4].shape[1])[None, :] < arr[3][:, None]
+        saved.append((arr[0], arr[1], arr[2], arr[3], arr[4][live], arr[5][live], eng.ignored()))
+        fleet.append(eng)
+        twins.append(twin)
+
+    def restore(engines):
+        for e, a in zip(engines, saved):
+            e.tree_load(a[0], a[1], a[2], edge_len=a[3], xedge=a[4], uedge=a[5], ignored=a[6])
+
+    t_multi, t_solo, stats_multi, stats_solo = [], [], None, None
+    for rep in range(reps + 1):                          # (the first pass warms the code objects up and is not counted)
+        restore(fleet)
+        restore(twins)
+        t0 = time.perf_counter()
+        done = Engine.tree_retain_multi(fleet, roots, True)
+        t1 = time.perf_counter()
+        solo = [twin.tree_retain(root, revalidate=True) for twin, root in zip(twins, roots)]
+        t2 = time.perf_counter()
+        stats_multi, stats_solo = [d[0] for d in done], [d[0] for d in solo]
+        assert stats_multi == stats_solo
+        if rep > 0:
+            t_multi.append(t1 - t0)
+            t_solo.append(t2 - t1)
+    sizes = [s["old_size"] for s in stats_multi]
+    kept = [s["kept"] for s in stats_multi]
+    for e in fleet + twins:
+        e.close()
+    m, so = float(np.median(t_multi)), float(np.median(t_solo))
+    return dict(case="fleet", system="boat_advanced", trees=n, nodes_per_tree=int(np.median(sizes)), nodes_total=int(sum(sizes)),
+                kept_total=int(sum(kept)), kept_fraction=round(sum(kept) / float(sum(sizes)), 4), revalidate=True,
+                multi_call_ms=round(1e3 * m, 3), solo_loop_ms=round(1e3 * so, 3), solo_per_tree_ms=round(1e3 * so / n, 3),
+                multi_per_tree_ms=round(1e3 * m / n, 3), solo_over_multi=round(so / m, 2),
+                multi_call_ms_all=[round(1e3 * v, 3) for v in t_multi], solo_loop_ms_all=[round(1e3 * v, 3) for v in t_solo])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--cases", default="boat_1e4,boat_1e5,config5")
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fleet", default=None, help="fleet sizes, e.g. 4,16,64 or 16x100000 (trees x nodes): time tree_retain_multi against the loop of tree_retain")
+    ap.add_argument("--fleet-nodes", type=int, default=10000)
     a = ap.parse_args()
+    if a.fleet:
+        rows = []
+        for item in a.fleet.split(","):                  # "16" = 16 trees of --fleet-nodes nodes, "16x100000" = of 100000
+            n, _, nodes = item.partition("x")
+            rows.append(run_fleet(int(n), int(nodes) if nodes else a.fleet_nodes, a.reps))
+            print(json.dumps(rows[-1]), flush=True)
+        if a.out:
+            os.makedirs(a.out, exist_ok=True)
+            with open(os.path.join(a.out, "retain_multi_bench.jsonl"), "w") as f:
+                f.write("".join(json.dumps(r) + "\n" for r in rows))
+        return
     rows = []
     for case in a.cases.split(","):
         rows.append(run(case, a.reps, not a.no_host))
