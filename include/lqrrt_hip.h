@@ -418,6 +418,27 @@ int lqrrt_refine_search(lqrrt_engine* e, const int32_t* plan_host, int P, int go
 int lqrrt_refine_commit(lqrrt_engine* e, const int32_t* plan_host, int P, int goal_tries, int horizon_iters, int i, int j,
                         int32_t* ids_out, int cap_ids, void* stream);
 
+/* The two calls above for n engines at once (refine_plans): engine k refines plans[k] (plan_lens[k] node ids) with goal_tries[k]
+ * and horizon_iters[k]; horizon, goal tries, goal box and edge-pool length may differ between the engines, which share the device
+ * and the model (Riccati systems included); no engine appears twice, n <= 128.  EVERY argument of EVERY engine is checked with the
+ * rules of the one-engine calls before anything is written or launched.  Up to 32 engines share a launch (more: consecutive
+ * chunks on `stream`, also where one launch would exceed 2^32 threads), and the whole call waits for the stream once.  The few kB
+ * of device scratch behind a call are, like those of the one-engine calls, not part of lqrrt_engine_footprint.  Synchronous.
+ *
+ * lqrrt_refine_search_multi: one search launch per chunk, every engine with a best key of its own -- per engine the result of
+ * lqrrt_refine_search(incumbents[k]) in cost_out[k], i_out[k], j_out[k] (none: incumbents[k], -1, -1). */
+int lqrrt_refine_search_multi(lqrrt_engine** engines, int n, const int32_t* const* plans, const int32_t* plan_lens,
+                              const int32_t* goal_tries, const int32_t* horizon_iters, const int64_t* incumbents,
+                              int64_t* cost_out, int32_t* i_out, int32_t* j_out, void* stream);
+
+/* lqrrt_refine_commit_multi: one commit launch per chunk, one workgroup per engine with a candidate; i[k] = j[k] = -1 leaves
+ * engine k out (counts_out[k] = 0).  ids_out[k] [cap_ids[k] >= plan_lens[k]-1-j[k]+goal_tries[k]] receives engine k's new ids and
+ * counts_out[k] their number; counts_out[k] = LQRRT_E_CAPACITY when that tree cannot hold the chain, LQRRT_E_STATE when the chain
+ * does not reach the goal: that engine's tree and host mirrors are then unchanged, the others commit, and the call returns 0. */
+int lqrrt_refine_commit_multi(lqrrt_engine** engines, int n, const int32_t* const* plans, const int32_t* plan_lens,
+                              const int32_t* goal_tries, const int32_t* horizon_iters, const int32_t* i, const int32_t* j,
+                              int32_t* const* ids_out, const int32_t* cap_ids, int32_t* counts_out, void* stream);
+
 /* ---------------------------------------------------------------- wave engine -------- */
 
 /* Explicit sample stream: the caller supplies the samples (a user xrand_gen function,

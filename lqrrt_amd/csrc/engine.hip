@@ -83,8 +83,8 @@ static int fail(int code, const char* fmt, ...) {
 #include "engine_wave.hpp"        // ABI: wave_speculate / wave_commit / engine_extend
 #include "engine_sharded.hpp"     // ABI: comm_*, allgather_nodes, engine_extend_sharded
 #include "engine_multi.hpp"       // ABI: engine_extend_multi (several engines in lock step, two launches per tick)
-#include "engine_refine.hpp"      // ABI: refine_search / refine_commit (Planner.refine_plan)
 #include "engine_retain.hpp"      // ABI: tree_retain (Planner.replan)
+#include "engine_refine.hpp"      // ABI: refine_search / refine_commit (Planner.refine_plan; + _multi: retain_grid)
 
 // --------------------------------------------------------------------------------------------
 // Shader clock and issue rate, measured (bench.py reports them next to every latency-bound figure; tools/micro/clock.hip is

@@ -199,6 +199,8 @@ struct lqrrt_engine {
     int* d_ref = nullptr;
     int ref_cap = 0;
     unsigned long long* d_ref_key = nullptr;      // [4]: the key, then the three ints of k_refine_commit's output
+    char* d_refm = nullptr;                       // image of a multi-engine call's chunk that this engine leads (refine_multi_scratch)
+    size_t refm_cap = 0;
 
     // HBM held by this engine (lqrrt_engine_footprint): everything allocated at creation, and the H-dependent pools (alloc_wave)
     size_t bytes_fixed = 0, bytes_wave = 0, bytes_pinned = 0;

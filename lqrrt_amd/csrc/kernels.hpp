@@ -206,7 +206,7 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "steer.hpp"      // SteerFuse, steer_body, k_steer                          <- planner.py:354-438
 #include "ops.hpp"        // batched operators, k_steer_force, k_tree_root, k_append <- constraints.py:53-61, tree.py:50-96
 #include "multi.hpp"      // k_nn_scan_multi / k_steer_multi                         (build-only: several engines per launch)
-#include "refine.hpp"     // k_refine_search / k_refine_commit                       (Planner.refine_plan: shortcuts of a found plan)
 #include "retain.hpp"     // k_retain_*                                              (Planner.replan: re-root, re-validate, compact the tree)
+#include "refine.hpp"     // k_refine_search / k_refine_commit (+ _multi: RetainGrid) (Planner.refine_plan: shortcuts of a found plan)
 
 }  // namespace lq

@@ -140,22 +140,22 @@ __device__ __forceinline__ unsigned long long refine_best(const unsigned long lo
     return ((unsigned long long)hi << 32) | lo;
 }
 
-// Grid = P (P - 1) / 2 workgroups of one wavefront, candidate c <-> (i, j) row by row.  Dynamic LDS: the staged geometry,
-// then the edge rows [H][N] and [H][M], then the chain's current node.  *best holds the incumbent's key on entry and the
-// winner's on exit.
+// Candidate `cand` of one plan, c <-> (i, j) row by row, by one wavefront.  lds: the staged geometry, then the edge rows [H][N]
+// and [H][M], then the chain's current node.  *best holds the incumbent's key on entry and the winner's on exit.  Shared by
+// k_refine_search (the grid is one plan) and k_refine_search_multi (the grid spans the plans of a call; P / g / r / tv / a are
+// then references into device memory, read by scalar loads).
 template <class S>
-__global__ __launch_bounds__(64) void k_refine_search(Params P, Geo g, Res r, TreeView tv, RefineArgs a,
-                                                      unsigned long long* __restrict__ best) {
-    extern __shared__ double geo_lds[];
+__device__ __forceinline__ void refine_search_body(const Params& P, const Geo& g, const Res& r, const TreeView& tv, const RefineArgs& a,
+                                                   unsigned long long* __restrict__ best, double* lds, int cand) {
     __shared__ GainLds<S> gl_lds;
     const int lane = threadIdx.x;
-    int c = blockIdx.x, i = 0;
+    int c = cand, i = 0;
     while (c >= a.P - 1 - i) { c -= a.P - 1 - i; ++i; }
     const int j = i + 1 + c;
     int cost = a.prefix[i];
     if (refine_key(cost, i, j) > refine_best(best)) return;
-    const GeoL gl = stage_geo(g, geo_lds, lane, 64);
-    double* hx = geo_lds + geo_lds_doubles(g);
+    const GeoL gl = stage_geo(g, lds, lane, 64);
+    double* hx = lds + geo_lds_doubles(g);
     double* hu = hx + (size_t)a.H * S::N;
     double* cur = hu + (size_t)a.H * S::M;
     refine_start<S>(tv, a.plan[i], cur, lane);                  // (its barrier also covers the staged geometry)
@@ -174,20 +174,28 @@ __global__ __launch_bounds__(64) void k_refine_search(Params P, Geo g, Res r, Tr
     }
 }
 
+// Grid = P (P - 1) / 2 workgroups of one wavefront.  Dynamic LDS: refine_lds_bytes.
+template <class S>
+__global__ __launch_bounds__(64) void k_refine_search(Params P, Geo g, Res r, TreeView tv, RefineArgs a,
+                                                      unsigned long long* __restrict__ best) {
+    extern __shared__ double geo_lds[];
+    refine_search_body<S>(P, g, r, tv, a, best, geo_lds, (int)blockIdx.x);
+}
+
 // Replays candidate (i, j) in one workgroup and appends its non-empty edges as nodes base, base + 1, ... (parent chain below
 // p_i), with state, trig, K, parent, edge length, edge rows and -- when the sampler has fixed angles -- the angle errors
 // (TreeView::werr).  out[0] = the number of nodes appended, or -1 when the chain does not fit below tv.cap (then nothing
 // at or above the tree size is meaningful and the caller keeps its size); out[1] = the chain's cost; out[2] = 1 when it ended
-// in the goal box.
+// in the goal box.  lens (may be null): the appended nodes' edge lengths once more, in order, where the host finds those of a
+// whole call in one copy.
 template <class S>
-__global__ __launch_bounds__(64) void k_refine_commit(Params P, Geo g, Res r, TreeView tv, RefineArgs a, int i, int j, int base,
-                                                      FixedAngles fx, int* __restrict__ out) {
-    extern __shared__ double geo_lds[];
+__device__ __forceinline__ void refine_commit_body(const Params& P, const Geo& g, const Res& r, const TreeView& tv, const RefineArgs& a,
+                                                   int i, int j, int base, const FixedAngles& fx, int* __restrict__ out,
+                                                   int* __restrict__ lens, double* lds) {
     __shared__ GainLds<S> gl_lds;
-    if (blockIdx.x != 0) return;
     const int lane = threadIdx.x;
-    const GeoL gl = stage_geo(g, geo_lds, lane, 64);
-    double* hx = geo_lds + geo_lds_doubles(g);
+    const GeoL gl = stage_geo(g, lds, lane, 64);
+    double* hx = lds + geo_lds_doubles(g);
     double* hu = hx + (size_t)a.H * S::N;
     double* cur = hu + (size_t)a.H * S::M;
     int parent = a.plan[i], cost = a.prefix[i], added = 0, goal = 0;
@@ -211,7 +219,10 @@ __global__ __launch_bounds__(64) void k_refine_commit(Params P, Geo g, Res r, Tr
                 tv.werr[(size_t)lane * tv.cap + id] = wrap_err(fx.t[2 * lane], fx.t[2 * lane + 1], cur[S::N + 2 * lane],
                                                                cur[S::N + 2 * lane + 1]);
         }
-        if (lane == 0) { tv.pID[id] = parent; tv.elen[id] = len; }
+        if (lane == 0) {
+            tv.pID[id] = parent; tv.elen[id] = len;
+            if (lens) lens[added] = len;
+        }
         __syncthreads();                                         // the next edge overwrites the rows and the current node
         parent = id;
         ++added;
@@ -219,4 +230,47 @@ __global__ __launch_bounds__(64) void k_refine_commit(Params P, Geo g, Res r, Tr
         if (refine_in_goal<S>(r, cur)) { goal = 1; break; }
     }
     if (lane == 0) { out[0] = added; out[1] = cost; out[2] = goal; }
+}
+
+template <class S>
+__global__ __launch_bounds__(64) void k_refine_commit(Params P, Geo g, Res r, TreeView tv, RefineArgs a, int i, int j, int base,
+                                                      FixedAngles fx, int* __restrict__ out) {
+    extern __shared__ double geo_lds[];
+    if (blockIdx.x != 0) return;
+    refine_commit_body<S>(P, g, r, tv, a, i, j, base, fx, out, nullptr, geo_lds);
+}
+
+// ------------------------------------------------------------------------------------------
+// The same two stages for SEVERAL plans per launch (lqrrt_refine_search_multi / lqrrt_refine_commit_multi; refine_plans).  A search
+// round is bound by its longest chain, not by its width: the rounds of a fleet's plans run side by side in ONE launch.  As in
+// retain.hpp a workgroup finds its engine from the ascending prefix table of workgroup counts in the arguments (multi_engine_of)
+// and reads P / g / r / tv from that engine's device-resident EngineProto; what belongs to the call -- the plan, its cost prefix,
+// P, tries, H, the goal, the candidate to replay and where the results go -- is a RefineDesc per engine in device memory.  Every
+// engine has its OWN best key: the early stop prunes within one plan only, so each winner is the one the engine's own launch finds.
+struct RefineDesc {
+    RefineArgs a;
+    unsigned long long* best;     // search: the engine's key
+    int* out;                     // commit: the engine's out[3]
+    int* lens;                    // commit: the engine's slice of the edge lengths
+    int i, j, base, pad;          // commit: the candidate and the tree size
+};
+
+// Grid = the engines' P (P - 1) / 2 back to back.  Dynamic LDS: the largest refine_lds_bytes of the call.
+template <class S>
+__global__ __launch_bounds__(64) void k_refine_search_multi(ProtoTable pt, const RefineDesc* __restrict__ ds, RetainGrid gr) {
+    extern __shared__ double geo_lds[];
+    const int e = multi_engine_of(gr.block0, gr.n, (int)blockIdx.x);
+    const RefineDesc& d = ds[e];
+    const EngineProto& p = *pt.p[e];
+    refine_search_body<S>(p.P, p.g, p.r, p.tv, d.a, d.best, geo_lds, (int)blockIdx.x - gr.block0[e]);
+}
+
+// One workgroup per engine with a winner: ds and pt hold those engines only, in the same order.
+template <class S>
+__global__ __launch_bounds__(64) void k_refine_commit_multi(ProtoTable pt, const RefineDesc* __restrict__ ds, int n) {
+    extern __shared__ double geo_lds[];
+    if ((int)blockIdx.x >= n) return;
+    const RefineDesc& d = ds[blockIdx.x];
+    const EngineProto& p = *pt.p[blockIdx.x];
+    refine_commit_body<S>(p.P, p.g, p.r, p.tv, d.a, d.i, d.j, d.base, p.ra.fx, d.out, d.lens, geo_lds);
 }

@@ -456,6 +456,66 @@ class Engine(object):
                                                     nat.ptr(out), len(out), self._stream()))
         return out[:k].tolist()
 
+    @staticmethod
+    def _refine_multi_args(engines, plans, horizons, goal_tries):
+        engines = list(engines)
+        n = len(engines)
+        if n < 1:
+            raise ValueError("no engines")
+        plans = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in plans]
+        horizons = np.ascontiguousarray([int(h) for h in horizons], dtype=np.int32)
+        tries = np.ascontiguousarray(np.broadcast_to(np.asarray(goal_tries, dtype=np.int64), (n,)), dtype=np.int32)
+        if len(plans) != n or horizons.shape != (n,):
+            raise ValueError("expected one plan and one horizon per engine")
+        handles = (C.c_void_p * n)(*[e.h for e in engines])
+        plan_ptrs = (C.c_void_p * n)(*[p.ctypes.data for p in plans])
+        plan_lens = np.ascontiguousarray([len(p) for p in plans], dtype=np.int32)
+        return engines, n, handles, plans, plan_ptrs, plan_lens, horizons, tries
+
+    @staticmethod
+    def refine_round_multi(engines, plans, horizons, incumbents, goal_tries=8):
+        """refine_round for n engines in one native call (lqrrt_refine_search_multi): the searches of all plans share one kernel
+        launch, every engine with a best key of its own.  `plans`, `horizons`, `incumbents`: one per engine; `goal_tries`: one for
+        all or one per engine.  Returns [(cost, i, j) or None] in the engines' order, each what that engine's own refine_round
+        returns.  The engines share device and model; every argument is checked before anything is launched."""
+        engines, n, handles, plans, plan_ptrs, plan_lens, horizons, tries = Engine._refine_multi_args(engines, plans, horizons, goal_tries)
+        inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
+        if inc.shape != (n,):
+            raise ValueError("expected one incumbent per engine")
+        cost, i, j = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_refine_search_multi(handles, n, plan_ptrs, nat.ptr(plan_lens), nat.ptr(tries), nat.ptr(horizons),
+                                                      nat.ptr(inc), nat.ptr(cost), nat.ptr(i), nat.ptr(j), engines[0]._stream()))
+        return [None if i[k] < 0 else (int(cost[k]), int(i[k]), int(j[k])) for k in range(n)]
+
+    @staticmethod
+    def refine_commit_multi(engines, plans, horizons, ijs, goal_tries=8):
+        """refine_commit for n engines in one native call (lqrrt_refine_commit_multi): one workgroup per engine replays its
+        candidate ijs[k] = (i, j) below its own tree size (None: the engine is left out and gets []).  Returns a list of new-id
+        lists, None where the tree cannot hold the chain (that tree is unchanged; the others commit).  A candidate whose chain
+        does not reach the goal raises NativeError(E_STATE) after the other engines have committed; the error carries what they
+        appended (`results`: this list, `failed`: the indices of the engines that appended nothing for that reason)."""
+        engines, n, handles, plans, plan_ptrs, plan_lens, horizons, tries = Engine._refine_multi_args(engines, plans, horizons, goal_tries)
+        ijs = list(ijs)
+        if len(ijs) != n:
+            raise ValueError("expected one candidate per engine")
+        ci = np.ascontiguousarray([-1 if c is None else int(c[0]) for c in ijs], dtype=np.int32)
+        cj = np.ascontiguousarray([-1 if c is None else int(c[1]) for c in ijs], dtype=np.int32)
+        outs = [np.empty(max(len(plans[k]) - 1 - max(int(cj[k]), 0) + int(tries[k]), 1), dtype=np.int32) for k in range(n)]
+        out_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs])
+        caps = np.ascontiguousarray([len(a) for a in outs], dtype=np.int32)
+        counts = np.zeros(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_refine_commit_multi(handles, n, plan_ptrs, nat.ptr(plan_lens), nat.ptr(tries), nat.ptr(horizons),
+                                                      nat.ptr(ci), nat.ptr(cj), out_ptrs, nat.ptr(caps), nat.ptr(counts),
+                                                      engines[0]._stream()))
+        results = [None if counts[k] < 0 else outs[k][:counts[k]].tolist() for k in range(n)]
+        bad = [k for k in range(n) if counts[k] < 0 and counts[k] != nat.E_CAPACITY]
+        if bad:
+            err = nat.NativeError(int(counts[bad[0]]), "candidate (%d, %d) of engine %d does not reach the goal: nothing appended"
+                                  % (ci[bad[0]], cj[bad[0]], bad[0]))
+            err.results, err.failed = results, bad                  # what the other engines of the call committed
+            raise err
+        return results
+
     def push_samples(self, xs):
         xs = nat.as_f64(xs)
         if xs.ndim != 2 or xs.shape[1] != self.n:

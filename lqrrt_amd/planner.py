@@ -512,43 +512,66 @@ class Planner:
                                       "of the search would have to run; the device cannot call it.")
         if int(max_rounds) < 0 or int(goal_tries) < 1:
             raise ValueError("max_rounds must be >= 0 and goal_tries >= 1.")
-        tree, eng = self.tree, self._engine
-        if not self.plan_reached_goal or getattr(self, "node_seq", None) is None or tree is None or not tree.on_device \
-                or tree._e is not eng:
+        run = self._refine_begin()
+        if run is None:
             return 0
-        plan = [int(v) for v in self.node_seq]
-        finish = len(plan) > 1 and plan[-1] >= eng.size                    # the finish_on_goal node lives on the host (tree.add_node)
-        if tree._host_nodes() != (1 if finish else 0):
-            raise RuntimeError("refine_plan: the tree holds nodes added with Tree.add_node; refine before adding nodes by hand.")
-        core = plan[:-1] if finish else plan
-        H = int(self.horizon_iters)
-        rounds, error = 0, None
-        while rounds < int(max_rounds):
+        eng, error = self._engine, None
+        while run.rounds < int(max_rounds):
             try:
-                lens = eng.edge_lengths()
-                incumbent = 1 + int(sum(int(lens[p]) for p in core[1:]))
-                win = eng.refine_round(core, H, incumbent, goal_tries)
+                win = eng.refine_round(run.core, run.H, self._refine_incumbent(run), goal_tries)
                 if win is None:
                     break
-                _, i, j = win
-                ids = eng.refine_commit(core, H, i, j, goal_tries)
+                cost, i, j = win
+                ids = eng.refine_commit(run.core, run.H, i, j, goal_tries)
             except (nat.NativeError, ValueError) as ex:
                 if getattr(ex, "code", None) != nat.E_CAPACITY:
                     error = ex                                      # raised below, once the rounds already accepted are adopted
                 break
-            if rounds == 0 and finish:
-                tree._drop_host_tail()                                      # refined away; a new one follows below
-            core = core[:i + 1] + ids
-            rounds += 1
-        if rounds:
-            # the plan describes the tree as it now is, also when a later round failed (a failed commit appends nothing)
-            self._adopt_plan(core[-1])
-            if finish:
-                self._finish_on_goal()
-            self._prepare_interpolators()
+            self._refine_accept(run, cost, i, ids)
+        rounds = self._refine_end(run)
         if error is not None:
             raise error
         return rounds
+
+    # The three steps of a refinement that refine_plan (one planner, its engine's own calls) and refine_plans (a fleet, batched
+    # calls) share: what is refined, what a round's winner changes, what the planner adopts at the end.
+    def _refine_begin(self):
+        """The refinement's state (_RefineRun), or None when there is nothing to refine.  Reads only."""
+        tree, eng = self.tree, self._engine
+        if not self.plan_reached_goal or getattr(self, "node_seq", None) is None or tree is None or not tree.on_device \
+                or tree._e is not eng:
+            return None
+        plan = [int(v) for v in self.node_seq]
+        finish = len(plan) > 1 and plan[-1] >= eng.size                    # the finish_on_goal node lives on the host (tree.add_node)
+        if tree._host_nodes() != (1 if finish else 0):
+            raise RuntimeError("refine_plan: the tree holds nodes added with Tree.add_node; refine before adding nodes by hand.")
+        run = _RefineRun()
+        run.core, run.finish, run.H, run.rounds, run.cost = (plan[:-1] if finish else plan), finish, int(self.horizon_iters), 0, None
+        return run
+
+    def _refine_incumbent(self, run):
+        """Steps of the plan as it stands: what the next round has to beat (an accepted winner's cost is its plan's)."""
+        if run.cost is None:
+            lens = self._engine.edge_lengths()
+            run.cost = 1 + int(sum(int(lens[p]) for p in run.core[1:]))
+        return run.cost
+
+    def _refine_accept(self, run, cost, i, ids):
+        """A committed winner: the plan continues below core[i] with the appended nodes."""
+        if run.rounds == 0 and run.finish:
+            self.tree._drop_host_tail()                                     # refined away; a new one follows in _refine_end
+        run.core = run.core[:i + 1] + list(ids)
+        run.cost = int(cost)
+        run.rounds += 1
+
+    def _refine_end(self, run):
+        if run.rounds:
+            # the plan describes the tree as it now is, also when a later round failed (a failed commit appends nothing)
+            self._adopt_plan(run.core[-1])
+            if run.finish:
+                self._finish_on_goal()
+            self._prepare_interpolators()
+        return run.rounds
 
     def _in_goal(self, x):
         """True if x lies strictly inside the goal box (planner.py:442-447)."""
@@ -685,6 +708,11 @@ class Planner:
 
 class _PlanRun(object):
     """What update_plan keeps between native calls of one plan."""
+
+
+class _RefineRun(object):
+    """What refine_plan / refine_plans keep between the rounds of one planner: core (the plan without a finish_on_goal node), finish,
+    H (the fixed steer horizon), rounds accepted, cost (steps of core; None until counted)."""
 
 
 def update_plans(jobs):
@@ -875,3 +903,81 @@ def _add_stats(a, b):
     out.stop_reason = b.stop_reason
     out.candidates = b.candidates
     return out
+
+
+def refine_plans(planners, max_rounds=8, goal_tries=8):
+    """
+    refine_plan for a fleet: every planner gets exactly what its own refine_plan(max_rounds, goal_tries) gives it -- node_seq, x_seq,
+    u_seq, t_seq, T, the appended tree nodes, the interpolators, a finish_on_goal node dropped and steered again -- but the native
+    calls are shared.  The planners of one (device, native system type) form a group; each round is ONE search launch over the plans
+    of the group's still-active planners (Engine.refine_round_multi: a search is bound by its longest chain, not by its width, so the
+    rounds of many plans fit side by side) and ONE commit launch over those with a winner (Engine.refine_commit_multi).  A planner
+    leaves the active set at its fix-point, after max_rounds or when its tree cannot hold the next chain.  A planner with nothing to
+    refine (where refine_plan returns 0 at once) gets 0 and takes part in no launch.  Returns the list of accepted round counts.
+
+    Refused with ValueError for EVERY planner before any is touched: a planner that appears twice, a callback-mode planner, a tree
+    that holds hand-added host nodes.  If a native call fails, the rounds accepted so far are adopted by every planner -- those of
+    the failing commit call included, for the engines that did commit in it -- then the error is raised (as refine_plan does).
+    """
+    planners = list(planners)
+    if not planners:
+        return []
+    if len(set(id(p) for p in planners)) != len(planners):
+        raise ValueError("refine_plans: a planner appears twice.")
+    if int(max_rounds) < 0 or int(goal_tries) < 1:
+        raise ValueError("max_rounds must be >= 0 and goal_tries >= 1.")
+    for p in planners:
+        if not isinstance(p, Planner):
+            raise ValueError("refine_plans: expected Planner objects.")
+        if p.callback_mode:                                         # (as the last set_system left it, as in refine_plan)
+            raise ValueError("refine_plans: planners whose plugins are Python callables cannot be refined (the device cannot call them).")
+    runs = []
+    for p in planners:
+        try:
+            runs.append(p._refine_begin())
+        except RuntimeError as ex:
+            raise ValueError(str(ex).replace("refine_plan:", "refine_plans:"))
+    groups = {}
+    for k, (p, run) in enumerate(zip(planners, runs)):
+        if run is not None:
+            groups.setdefault((p.device, type(p.system)), []).append(k)
+    error = None
+    for g in sorted(groups, key=lambda g: groups[g][0]):
+        for first in range(0, len(groups[g]), 128):                 # (a native call takes at most 128 engines)
+            active = groups[g][first:first + 128]
+            try:
+                while True:
+                    active = [k for k in active if runs[k].rounds < int(max_rounds)]
+                    if not active:
+                        break
+                    wins = Engine.refine_round_multi([planners[k]._engine for k in active], [runs[k].core for k in active],
+                                                     [runs[k].H for k in active], [planners[k]._refine_incumbent(runs[k]) for k in active],
+                                                     goal_tries)
+                    winners = [(k, w) for k, w in zip(active, wins) if w is not None]
+                    if not winners:
+                        break
+                    failed = None
+                    try:
+                        new = Engine.refine_commit_multi([planners[k]._engine for k, _ in winners], [runs[k].core for k, _ in winners],
+                                                         [runs[k].H for k, _ in winners], [(w[1], w[2]) for _, w in winners], goal_tries)
+                    except nat.NativeError as ex:
+                        if getattr(ex, "results", None) is None:
+                            raise
+                        new, failed = ex.results, ex                # the other engines of the call did commit: their plans follow
+                    active = []
+                    for (k, w), ids in zip(winners, new):
+                        if ids is None:                             # capacity (or a failed chain): this planner stops with what it has
+                            continue
+                        planners[k]._refine_accept(runs[k], w[0], w[1], ids)
+                        active.append(k)
+                    if failed is not None:
+                        raise failed
+            except (nat.NativeError, ValueError) as ex:
+                error = ex                                          # raised below, once the rounds already accepted are adopted
+                break
+        if error is not None:
+            break
+    results = [0 if run is None else p._refine_end(run) for p, run in zip(planners, runs)]
+    if error is not None:
+        raise error
+    return results
