@@ -439,6 +439,32 @@ int lqrrt_refine_commit_multi(lqrrt_engine** engines, int n, const int32_t* cons
                               const int32_t* goal_tries, const int32_t* horizon_iters, const int32_t* i, const int32_t* j,
                               int32_t* const* ids_out, const int32_t* cap_ids, int32_t* counts_out, void* stream);
 
+/* Tree-wide goal connection (Planner.connect_goal; not in the reference): from which node of the WHOLE tree does a short chain of
+ * goal-directed steers reach the goal, and which gives the shortest plan?  For a tree of N nodes with pID[v] < v, depth[0] = 1 and
+ * depth[v] = depth[pID[v]] + L_v (L_v the node's edge length).  A candidate is a node v -- every node (nodes_host = NULL; count is
+ * then ignored) or those of nodes_host [count], in any order -- and starts at v's state and gain at cost depth[v].  Its targets are
+ * the goal, up to goal_tries times, one edge each: planner.py:354-438 with a fixed horizon of horizon_iters steps, the FPR cut, no
+ * adaptive heuristic; an empty edge adds nothing, a non-empty one moves the chain to its end state with lqr(x_end, u_last)[1].
+ * The chain is valid when an edge ends strictly inside the goal box, and ends there; when the tries run out first it is invalid.  A
+ * candidate that itself lies in the goal box needs a non-empty edge like any other.
+ *
+ * lqrrt_connect_search: the valid candidate of smallest (cost, node id) with cost < incumbent -> *cost, *node_out; none:
+ * *cost = incumbent, *node_out = -1.  incumbent in [1, 2^31-1]; 2^31-1: no plan to beat.  One launch, one wavefront per candidate,
+ * with a global early stop that cannot change the winner; synchronous.  The depth table is computed on the host from the engine's
+ * mirrors and uploaded with the call; it lives in device scratch that grows on demand (4 B per node plus the id list) and is, like
+ * that of lqrrt_refine_search, not part of lqrrt_engine_footprint. */
+int lqrrt_connect_search(lqrrt_engine* e, const int32_t* nodes_host, int count, int goal_tries, int horizon_iters,
+                         int64_t incumbent, int64_t* cost, int32_t* node_out, void* stream);
+
+/* lqrrt_connect_commit: replays the chain of candidate `node` and appends its non-empty edges to the tree as a parent chain below
+ * it (as lqrrt_refine_commit: state, gain, parent, edge, angle-error table; host mirrors and ignore set stay valid, the new nodes
+ * are not ignored).  ids_out [cap_ids >= goal_tries] receives the new ids; returns their count.  LQRRT_E_CAPACITY when the tree
+ * cannot hold the chain, LQRRT_E_STATE when the chain does not reach the goal: the tree is then unchanged.  The loop-time goal
+ * bookkeeping (lqrrt_plan_best) is not rewritten; a later lqrrt_tree_retain rebuilds it and sees the chain's last node as a hit.
+ * Synchronous. */
+int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, int32_t* ids_out, int cap_ids,
+                         void* stream);
+
 /* ---------------------------------------------------------------- wave engine -------- */
 
 /* Explicit sample stream: the caller supplies the samples (a user xrand_gen function,

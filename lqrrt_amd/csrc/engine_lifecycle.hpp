@@ -34,7 +34,7 @@ static void free_all(lqrrt_engine* e) {
                     e->d_pidx, e->d_par_done, e->d_par_want, e->d_list,
                     e->d_changed, e->d_stale, e->d_need, e->d_summary, e->d_pool, e->d_pool_trig, e->d_pool_S, e->d_QR, e->d_Sop, e->d_cand, e->d_flags,
                     e->d_M2, e->d_lf[0], e->d_lf[1], e->d_par2, e->d_stale2, e->d_changed2, e->d_head2, e->d_rctl, e->d_rank,
-                    e->d_blk, e->d_blk_cursor, e->d_ref, e->d_ref_key, e->d_refm};
+                    e->d_blk, e->d_blk_cursor, e->d_ref, e->d_ref_key, e->d_refm, e->d_con};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (e->h_ign_pin) (void)hipHostFree(e->h_ign_pin);

@@ -201,6 +201,10 @@ struct lqrrt_engine {
     unsigned long long* d_ref_key = nullptr;      // [4]: the key, then the three ints of k_refine_commit's output
     char* d_refm = nullptr;                       // image of a multi-engine call's chunk that this engine leads (refine_multi_scratch)
     size_t refm_cap = 0;
+    // goal connection (engine_connect.hpp): 8 ints of results (the best key, then k_refine_commit's three outputs), then the depth table
+    // and the candidate ids of a search, or the one-node plan of a commit; grown on demand, like d_ref not part of the footprint
+    int* d_con = nullptr;
+    size_t con_cap = 0;                           // ints behind the 8 of the head
 
     // HBM held by this engine (lqrrt_engine_footprint): everything allocated at creation, and the H-dependent pools (alloc_wave)
     size_t bytes_fixed = 0, bytes_wave = 0, bytes_pinned = 0;

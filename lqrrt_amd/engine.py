@@ -516,6 +516,25 @@ class Engine(object):
             raise err
         return results
 
+    # -- tree-wide goal connection (csrc/engine_connect.hpp; the rule: tests/connect_reference.py) ---------
+    def connect_search(self, horizon_iters, incumbent, goal_tries=8, nodes=None):
+        """(cost, node) of the tree node -- any node, or one of `nodes` -- whose chain of up to `goal_tries` steers toward the goal
+        reaches it in the fewest steps from the root, fewer than `incumbent`; None when there is none (lqrrt_connect_search)."""
+        ids = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        cost, node = C.c_int64(), C.c_int32()
+        nat.check(nat.lib().lqrrt_connect_search(self.h, None if ids is None else nat.ptr(ids), 0 if ids is None else len(ids),
+                                                 int(goal_tries), int(horizon_iters), int(incumbent), C.byref(cost), C.byref(node),
+                                                 self._stream()))
+        return None if node.value < 0 else (cost.value, node.value)
+
+    def connect_commit(self, node, horizon_iters, goal_tries=8):
+        """Appends the goal chain of candidate `node` below it (lqrrt_connect_commit); returns the new node ids.  NativeError with
+        code E_CAPACITY when the tree cannot hold it, E_STATE when the chain does not reach the goal (the tree is then unchanged)."""
+        out = np.empty(max(int(goal_tries), 1), dtype=np.int32)
+        k = nat.check(nat.lib().lqrrt_connect_commit(self.h, int(node), int(goal_tries), int(horizon_iters), nat.ptr(out), len(out),
+                                                     self._stream()))
+        return out[:k].tolist()
+
     def push_samples(self, xs):
         xs = nat.as_f64(xs)
         if xs.ndim != 2 or xs.shape[1] != self.n:

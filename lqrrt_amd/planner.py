@@ -273,6 +273,7 @@ class Planner:
         if retained is not None:
             x0 = eng.states(0, 1)[0]
         self._grown_with = self._tree_resolution()
+        self._grown_goal = np.array(self.goal, dtype=np.float64)    # (the engine's goal box: what connect_goal steers at)
         if not run.user_sampler:
             space, bias, tries_limit = run.sampler
             eng.set_sampler(np.mean(space, axis=1), np.diff(space).flatten(), bias, tries_limit)
@@ -535,10 +536,11 @@ class Planner:
 
     # The three steps of a refinement that refine_plan (one planner, its engine's own calls) and refine_plans (a fleet, batched
     # calls) share: what is refined, what a round's winner changes, what the planner adopts at the end.
-    def _refine_begin(self):
-        """The refinement's state (_RefineRun), or None when there is nothing to refine.  Reads only."""
+    def _refine_begin(self, need_goal=True):
+        """The refinement's state (_RefineRun), or None when there is nothing to refine.  Reads only.  connect_goal (need_goal=False)
+        also takes a plan that did not reach the goal."""
         tree, eng = self.tree, self._engine
-        if not self.plan_reached_goal or getattr(self, "node_seq", None) is None or tree is None or not tree.on_device \
+        if (need_goal and not self.plan_reached_goal) or getattr(self, "node_seq", None) is None or tree is None or not tree.on_device \
                 or tree._e is not eng:
             return None
         plan = [int(v) for v in self.node_seq]
@@ -572,6 +574,52 @@ class Planner:
                 self._finish_on_goal()
             self._prepare_interpolators()
         return run.rounds
+
+    def connect_goal(self, goal_tries=8, nodes=None, finish_on_goal=None):
+        """
+        Asks the WHOLE tree of the last plan the question the loop never asks (it steers a goal-biased sample from the one nearest
+        node only): from which node does a short chain of goal-directed steers reach the goal, and which gives the shortest plan?
+        Not in the reference.  Every node v (or those of the id list `nodes`) is a candidate: from v's state and gain, steer toward
+        the goal up to `goal_tries` times, one _steer(force_arrive=False) edge per try with the fixed horizon `horizon_iters` (no
+        adaptive heuristic), until an edge ends inside the goal region.  The candidate with the fewest steps from the root (ties to
+        the smaller node id) wins if it beats the current plan -- any valid chain does when that plan did not reach the goal, the
+        fallback of a budget that ran out ("Didn't reach goal.").  Its edges are appended to the tree below v and the plan becomes
+        climb(v) + the new nodes; plan_reached_goal is set.  The search is one kernel launch on the device (csrc/connect.hpp);
+        tests/connect_reference.py restates the rule.  refine_plan() may follow and starts from the new plan.
+
+        `finish_on_goal`: run the exact-goal steer from the new last node -- True / False, or None: as the replaced plan had it (a
+        fallback plan has none).  Returns True when the plan was replaced; False, with everything unchanged, when there is no tree
+        of this planner on the device, no chain is shorter, or the tree cannot hold the winner's chain.
+        """
+        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
+            raise NotImplementedError("connect_goal: in callback mode the steer is the user's Python function, which every candidate "
+                                      "of the search would have to run; the device cannot call it.")
+        if int(goal_tries) < 1:
+            raise ValueError("goal_tries must be >= 1.")
+        run = self._refine_begin(need_goal=False)
+        if run is None:
+            return False
+        if not np.array_equal(self.goal, self._grown_goal):
+            raise RuntimeError("connect_goal: the goal changed since the tree was grown; use update_plan or replan.")
+        eng = self._engine
+        incumbent = self._refine_incumbent(run) if self.plan_reached_goal else 2 ** 31 - 1
+        win = eng.connect_search(run.H, incumbent, goal_tries, nodes)
+        if win is None:
+            return False
+        cost, node = win
+        try:
+            ids = eng.connect_commit(node, run.H, goal_tries)
+        except nat.NativeError as ex:
+            if ex.code == nat.E_CAPACITY:
+                return False
+            raise
+        run.core = eng.climb(node)                                  # the plan continues below `node`, its last node
+        self._refine_accept(run, cost, len(run.core) - 1, ids)
+        if finish_on_goal is not None:
+            run.finish = bool(finish_on_goal)
+        self.plan_reached_goal = True
+        self._refine_end(run)
+        return True
 
     def _in_goal(self, x):
         """True if x lies strictly inside the goal box (planner.py:442-447)."""

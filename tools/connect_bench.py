@@ -1,0 +1,143 @@
+"""
+Time of the tree-wide goal connection (Planner.connect_goal: Engine.connect_search) on the device, next to the host time of the
+C-oracle reference of the same rule (tests/connect_reference.py, one core) on the same tree.  Times are host wall clock around the
+synchronous call (depth pass, upload, launch, read-back included), warmed, median of `--reps` with the lowest and the highest.
+
+Trees: the boat_advanced_10k fixture cut off before its first goal node (3308 nodes, no incumbent); the whole fixture tree with no
+incumbent and no id list (every chain runs until one wins); a boat_advanced tree of 10^5 nodes grown natively (no incumbent, the
+found plan's cost as incumbent, and the 1024 nodes nearest the goal as id list).  One refine_round on the fixture's 113-node plan is
+timed in the same process for scale.
+
+    python tools/connect_bench.py [--reps 3] [--nodes 100000] [--out DIR]   ->  one JSON line per case; DIR/connect_bench.jsonl
+    python tools/connect_bench.py --once                                     ->  one untimed search per case (for a kernel trace)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import lqrrt_amd                                       # noqa: E402
+import connect_reference as cr                         # noqa: E402
+from lqrrt_amd.engine import Engine                    # noqa: E402
+
+
+def timed(fn, reps):
+    fn()                                                 # (warms the code object up; not counted)
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(1e3 * (time.perf_counter() - t0))
+    return out, dict(ms=round(float(np.median(ts)), 3), ms_min=round(min(ts), 3), ms_max=round(max(ts), 3))
+
+
+def reference(ref, **kw):
+    t0 = time.perf_counter()
+    win = ref.search(**kw)
+    return (None if win is None else (win[0], win[1])), round(time.perf_counter() - t0, 3)
+
+
+def search_case(label, eng, ref, H, reps, once, incumbent=cr.NO_INCUMBENT, nodes=None, with_reference=True, **extra):
+    if once:
+        eng.connect_search(H, incumbent, nodes=nodes)
+        return None
+    got, t = timed(lambda: eng.connect_search(H, incumbent, nodes=nodes), reps)
+    row = dict(case=label, nodes=eng.size, candidates=eng.size if nodes is None else len(nodes),
+               incumbent=None if incumbent == cr.NO_INCUMBENT else int(incumbent), winner=got, device_ms=t["ms"],
+               device_ms_min=t["ms_min"], device_ms_max=t["ms_max"], **extra)
+    print("device: " + json.dumps(row), file=sys.stderr, flush=True)   # (the reference of a large tree takes a while)
+    if with_reference:
+        want, secs = reference(ref, incumbent=incumbent, nodes=nodes)
+        assert want == got, (label, want, got)
+        row["reference_s"] = secs
+    return row
+
+
+def fixture_engine(s, g, size):
+    kw = s.plan_kwargs
+    N = len(g["state"]) if size is None else size
+    el = np.array(g["edge_len"][:N], dtype=np.int32)
+    el[0] = 1
+    eng = Engine(s, capacity=N + 256, max_wave=64)
+    eng.set_resolution(kw["dt"], kw["FPR"], max(int(el.max()), cr.horizon_of(s, g)), np.abs(np.asarray(s.error_tol, dtype=np.float64)),
+                       s.goal, s.goal_buffer)
+    eng.tree_load(g["state"][:N], g["K"][:N], g["pID"][:N], edge_len=el)
+    return eng
+
+
+def run_fixture(reps, once):
+    s, g = cr.case("boat_advanced_10k")
+    rows = []
+    for label, size in (("boat_advanced_10k prefix", cr.first_goal_node(s, g)), ("boat_advanced_10k full", None)):
+        ref = cr.from_fixture(s, g, size)
+        eng = fixture_engine(s, g, size)
+        row = search_case(label, eng, ref, ref.H, reps, once)
+        rows.append(row)
+        if size is None and not once:
+            plan = [int(v) for v in g["node_seq"]]
+            _, t = timed(lambda: eng.refine_round(plan, ref.H, ref.cost(plan)), reps)
+            rows.append(dict(case="refine_round on the fixture plan, same tree", plan_nodes=len(plan), device_ms=t["ms"],
+                             device_ms_min=t["ms_min"], device_ms_max=t["ms_max"]))
+        if row is not None and size is not None:
+            t0 = time.perf_counter()
+            ids = eng.connect_commit(row["winner"][1], ref.H)
+            row["commit_ms_once"] = round(1e3 * (time.perf_counter() - t0), 3)
+            row["appended"] = len(ids)
+        eng.close()
+    return rows
+
+
+def run_native(max_nodes, reps, once):
+    s = lqrrt_amd.systems.BoatAdvanced(0)
+    cons = lqrrt_amd.Constraints(s.nstates, s.ncontrols, s.goal_buffer, s.is_feasible)
+    p = lqrrt_amd.Planner(s.dynamics, s.lqr, cons, error_tol=s.error_tol, erf=s.erf, goal0=s.goal, printing=False, min_time=2, max_time=3,
+                          max_nodes=max_nodes, sys_time=lambda: 0.0, wave_size=1024, **s.plan_kwargs)
+    np.random.seed(1)
+    t0 = time.perf_counter()
+    p.update_plan(s.x0, s.sample_space, goal_bias=s.goal_bias, xrand_gen=10)
+    grow_s = time.perf_counter() - t0
+    eng, H = p._engine, p.horizon_iters
+    ref = cr.Connector(s, eng.states(), eng.gains(), eng.parents(), eng.edge_lengths(), H)
+    label = "boat_advanced native %d" % eng.size
+    extra = dict(grow_s=round(grow_s, 2))
+    rows = [search_case(label + ", no incumbent", eng, ref, H, reps, once, **extra)]
+    if p.plan_reached_goal:
+        lens = eng.edge_lengths()
+        cost = 1 + int(sum(int(lens[v]) for v in p.node_seq[1:]))
+        rows.append(search_case(label + ", the plan's cost as incumbent", eng, ref, H, reps, once, incumbent=cost, **extra))
+    near = np.argsort(eng.costs_to_go(np.asarray(s.goal, dtype=np.float64)), kind="stable")[:1024].astype(np.int32)
+    rows.append(search_case(label + ", the 1024 nodes nearest the goal", eng, ref, H, reps, once, nodes=near, **extra))
+    # one candidate: what the call costs before any chain runs (the host's depth pass over the mirrors, the upload, one launch)
+    rows.append(search_case(label + ", the root alone", eng, ref, H, reps, once, nodes=np.zeros(1, dtype=np.int32), **extra))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--nodes", type=int, default=100000, help="size of the natively grown tree (0: leave it out)")
+    ap.add_argument("--once", action="store_true", help="one untimed search per case, no reference (for a kernel trace)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rows = run_fixture(a.reps, a.once)
+    if a.nodes > 0:
+        rows += run_native(a.nodes, a.reps, a.once)
+    rows = [r for r in rows if r is not None]
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    if a.out and rows:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "connect_bench.jsonl"), "w") as f:
+            f.write("".join(json.dumps(r) + "\n" for r in rows))
+
+
+if __name__ == "__main__":
+    main()
