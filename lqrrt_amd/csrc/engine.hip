@@ -18,6 +18,7 @@
 #include "../../include/lqrrt_hip.h"
 #include "kernels.hpp"
 #include "generic.hpp"
+#include "generic_sizes.hpp"
 #include "switches.hpp"
 
 #include <hip/hip_runtime.h>

@@ -12,8 +12,8 @@
 // the padded kernel width for the engine's n (generic.hpp: 7 or 12 states, trailing zeros change no bit)
 static int generic_width(const lqrrt_engine* e) { return e->n < 8 ? 7 : 12; }
 
-// partial minima of a generic scan: per sample, per 256-node workgroup, {eligible, overall}
-static size_t generic_blocks(const lqrrt_engine* e) { return std::min<size_t>(((size_t)e->cap + 255) / 256, 4096); }
+// partial minima of a generic scan: per sample, per workgroup, {eligible, overall} pairs -- counts from generic_sizes.hpp
+static size_t generic_pairs(const lqrrt_engine* e) { return generic_pairs_allocated((size_t)e->cap, (size_t)e->maxW, e->wide); }
 
 static int generic_create(lqrrt_engine* e, const lqrrt_system_desc* sys) {
     // params[0] = number of angular states, params[1 ..] their indices (ascending, distinct)
@@ -54,8 +54,8 @@ static int generic_create(lqrrt_engine* e, const lqrrt_system_desc* sys) {
     TRY(dalloc(&e->tv.pID, (size_t)e->cap));
     TRY(dalloc(&e->tv.ignore, (size_t)e->cap / 64 + 1));
     HIPCHK(hipMemset(e->tv.ignore, 0, sizeof(unsigned long long) * ((size_t)e->cap / 64 + 1)));
-    TRY(dalloc(&e->d_pcost, generic_blocks(e) * 2 * e->maxW));
-    TRY(dalloc(&e->d_pidx, generic_blocks(e) * 2 * e->maxW));
+    TRY(dalloc(&e->d_pcost, generic_pairs(e) * 2));
+    TRY(dalloc(&e->d_pidx, generic_pairs(e) * 2));
     if (hipHostMalloc((void**)&e->h_ign_pin, sizeof(unsigned long long) * ((size_t)e->cap / 64 + 1), hipHostMallocDefault) != hipSuccess)
         return fail(LQRRT_E_HIP, "hipHostMalloc failed");
     e->h_pid.reserve(e->cap);
@@ -103,9 +103,11 @@ static int generic_nn(lqrrt_engine* e, const GenericQuery* q, bool dense, const 
                       int32_t* id_dev, double* cost_dev, hipStream_t st, double seq, const double* errors_dev = nullptr) {
     GenericView v = generic_view(e, use_ignore);
     v.errors = errors_dev;
+    if (e->wide && xs) return fail(LQRRT_E_STATE, "the device-form batch query serves tables of up to %d states; use lqrrt_nn_argmin_host", LQRRT_MAX_STATES);
+    if (generic_pairs_written((size_t)e->N, (size_t)W, e->wide) > generic_pairs(e))
+        return fail(LQRRT_E_CAPACITY, "scan of %d nodes x %d queries exceeds the partial buffers", e->N, W);
     if (e->wide) {
-        if (xs) return fail(LQRRT_E_STATE, "the device-form batch query serves tables of up to %d states; use lqrrt_nn_argmin_host", LQRRT_MAX_STATES);
-        const int nbw = std::min((e->N + 63) / 64, 4096);
+        const int nbw = (int)generic_scan_blocks((size_t)e->N, true);
         WideArgs a;
         a.q = e->d_wq[0]; a.wk = e->d_wk; a.n = e->n; a.nw = e->gsh.nw;
         const size_t lds = sizeof(double) * 64 * (size_t)e->n;
@@ -117,7 +119,7 @@ static int generic_nn(lqrrt_engine* e, const GenericQuery* q, bool dense, const 
         e->wide_append_pending = false;          // the caller waits for this query: everything queued before it has completed by then
         return 0;
     }
-    const int nb = std::min((e->N + 255) / 256, 4096);       // beyond a million nodes a workgroup strides over several 256-node tiles
+    const int nb = (int)generic_scan_blocks((size_t)e->N, false);   // beyond a million nodes a workgroup strides over several 256-node tiles
     dim3 grid(nb, W);
     GenericQuery q0;
     if (!q) { memset(&q0, 0, sizeof q0); q = &q0; }
@@ -211,15 +213,19 @@ static int generic_reset(lqrrt_engine* e, const double* x0_host, hipStream_t st)
 
 static int generic_load(lqrrt_engine* e, int count, const double* states, const int32_t* pID, const uint8_t* ignored, hipStream_t st) {
     HIPCHK(hipStreamSynchronize(st));
-    std::vector<double> soa((size_t)count);
-    for (int d = 0; d < e->n; ++d) {
-        for (int i = 0; i < count; ++i) soa[i] = states[(size_t)i * e->n + d];
-        HIPCHK(hipMemcpy(e->tv.state + (size_t)d * e->cap, soa.data(), sizeof(double) * count, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(e->tv.pID, pID, sizeof(int) * count, hipMemcpyHostToDevice));
+    // Every copy is queued on `st`, the stream of the trig kernel that reads what they wrote: the order holds on any stream, a
+    // non-blocking one included.  The staging (all components, transposed once) and the caller's pID outlive the copies: the
+    // stream is waited for below, before this function returns.
+    std::vector<double> soa((size_t)count * e->n);
+    for (int d = 0; d < e->n; ++d)
+        for (int i = 0; i < count; ++i) soa[(size_t)d * count + i] = states[(size_t)i * e->n + d];
+    for (int d = 0; d < e->n; ++d)
+        HIPCHK(hipMemcpyAsync(e->tv.state + (size_t)d * e->cap, soa.data() + (size_t)d * count, sizeof(double) * count, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(e->tv.pID, pID, sizeof(int) * count, hipMemcpyHostToDevice, st));
     if (e->wide) hipLaunchKernelGGL(k_generic_trig_wide, dim3((count + 255) / 256), dim3(256), 0, st, e->tv.state, e->tv.trig, e->cap, count, e->n, e->d_wk);
     else hipLaunchKernelGGL(k_generic_trig, dim3((count + 255) / 256), dim3(256), 0, st, e->tv.state, e->tv.trig, e->cap, 0, count, e->gsh);
     HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));                       // the staging above is released on return
     e->h_pid.assign(pID, pID + count);
     e->h_elen.assign(count, 1);
     tree_bookkeeping_reset(e);

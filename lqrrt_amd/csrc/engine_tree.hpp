@@ -39,10 +39,21 @@ static int range_ok(lqrrt_engine* e, int first, int count) {
     return 0;
 }
 
+// LQRRT_MODEL_GENERIC appends are small launches on the caller's stream (lqrrt_tree_append) and the read-backs below are blocking
+// copies on the null stream: a non-blocking stream is not ordered against those, so a read-back right after an append waits for
+// the device first.  (Compiled-in models append through blocking copies or inside calls that wait for their stream.)  The wait is
+// for the whole device on purpose: the read-back ABI carries no stream argument, so the stream of the appends is not known here.
+// The read-backs are off the query path (the callback planner reads the table back when it hands its tree over).
+static int drain_appends(lqrrt_engine* e) {
+    if (e->generic) HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
 extern "C" int lqrrt_tree_get_states(lqrrt_engine* e, int first, int count, double* out) {
     TRY(range_ok(e, first, count));
     if (!count) return 0;
     TRY(use_device(e));
+    TRY(drain_appends(e));
     std::vector<double> tmp((size_t)count);
     for (int d = 0; d < e->n; ++d) {
         HIPCHK(hipMemcpy(tmp.data(), e->tv.state + (size_t)d * e->cap + first, sizeof(double) * count, hipMemcpyDeviceToHost));
@@ -64,6 +75,7 @@ extern "C" int lqrrt_tree_get_parents(lqrrt_engine* e, int first, int count, int
     TRY(range_ok(e, first, count));
     if (!count) return 0;
     TRY(use_device(e));
+    TRY(drain_appends(e));
     HIPCHK(hipMemcpy(out, e->tv.pID + first, sizeof(int) * count, hipMemcpyDeviceToHost));
     return 0;
 }

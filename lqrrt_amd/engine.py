@@ -632,6 +632,9 @@ class NodeTable(object):
     An LQRRT_MODEL_GENERIC engine (include/lqrrt_hip.h): the node table of a tree whose plugins are host callables -- SoA states,
     cos/sin of the angular ones, parents, ignore set -- and the nearest-neighbour stage over it (planner.py:239-247, 340-350).
     No dynamics, lqr or feasibility is compiled in; gains and edges stay with the caller (lqrrt_amd/callback.py).
+
+    angle_dims: the indices of the angular states, in ascending order, distinct and below nstates.  Anything else raises ValueError
+    before an engine is created (the indices are not sorted or de-duplicated here).
     """
 
     def __init__(self, nstates, ncontrols, angle_dims=(), capacity=100008, device=0, max_wave=64):
@@ -639,7 +642,10 @@ class NodeTable(object):
         self.n, self.m, self.device = int(nstates), int(ncontrols), device
         if not 1 <= self.n <= 64:
             raise ValueError("the device node table holds 1 to 64 states per node, got %d" % self.n)
-        self.angle_dims = tuple(sorted(int(d) for d in angle_dims))
+        self.angle_dims = tuple(int(d) for d in angle_dims)
+        # refused here, before an engine exists: the native table takes the indices as they come (ascending, distinct, < nstates)
+        if any(not 0 <= d < self.n for d in self.angle_dims) or any(a >= b for a, b in zip(self.angle_dims, self.angle_dims[1:])):
+            raise ValueError("angle_dims must be distinct state indices below %d in ascending order, got %r" % (self.n, self.angle_dims))
         d = nat.SystemDesc()
         d.model, d.nstates, d.ncontrols = nat.MODEL_GENERIC, self.n, self.m
         d.n_params = 1 + len(self.angle_dims)
