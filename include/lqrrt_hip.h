@@ -465,6 +465,29 @@ int lqrrt_connect_search(lqrrt_engine* e, const int32_t* nodes_host, int count, 
 int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, int32_t* ids_out, int cap_ids,
                          void* stream);
 
+/* The two calls above for n engines at once (connect_goals), with the conventions of lqrrt_refine_*_multi: horizon, goal tries,
+ * goal box and tree size may differ between the engines, which share the device and the model (Riccati systems included); no
+ * engine appears twice, n <= 128.  EVERY argument of EVERY engine is checked with the rules of the one-engine calls before
+ * anything is written or launched.  Up to 32 engines share a launch (more: consecutive chunks on `stream`, also where one launch
+ * would exceed 2^32 threads), and the whole call waits for the stream once.  The device scratch behind a call (4 B per node of
+ * every tree of a chunk plus the id lists, held by the chunk's first engine) is not part of lqrrt_engine_footprint.  Synchronous.
+ *
+ * lqrrt_connect_search_multi: one search launch per chunk, every engine with a best key of its own (the early stop prunes within
+ * one tree only) -- per engine the result of lqrrt_connect_search(incumbents[k]) in cost_out[k], node_out[k] (none:
+ * incumbents[k], -1).  nodes = NULL: every node of every tree; else nodes[k] = NULL: every node of tree k, or its id list
+ * [counts[k]].  An engine with an empty id list takes part in no launch and has no winner. */
+int lqrrt_connect_search_multi(lqrrt_engine** engines, int n, const int32_t* const* nodes, const int32_t* counts,
+                               const int32_t* goal_tries, const int32_t* horizon_iters, const int64_t* incumbents,
+                               int64_t* cost_out, int32_t* node_out, void* stream);
+
+/* lqrrt_connect_commit_multi: one commit launch per chunk, one workgroup per engine with a candidate; nodes[k] = -1 leaves engine k
+ * out (counts_out[k] = 0).  ids_out[k] [cap_ids[k] >= goal_tries[k]] receives engine k's new ids and counts_out[k] their number;
+ * counts_out[k] = LQRRT_E_CAPACITY when that tree cannot hold the chain, LQRRT_E_STATE when the chain does not reach the goal:
+ * that engine's tree and host mirrors are then unchanged, the others commit, and the call returns 0. */
+int lqrrt_connect_commit_multi(lqrrt_engine** engines, int n, const int32_t* nodes, const int32_t* goal_tries,
+                               const int32_t* horizon_iters, int32_t* const* ids_out, const int32_t* cap_ids, int32_t* counts_out,
+                               void* stream);
+
 /* ---------------------------------------------------------------- wave engine -------- */
 
 /* Explicit sample stream: the caller supplies the samples (a user xrand_gen function,

@@ -71,3 +71,38 @@ __global__ __launch_bounds__(64) void k_connect_search(Params P, Geo g, Res r, T
     extern __shared__ double geo_lds[];
     connect_search_body<S>(P, g, r, tv, a, best, geo_lds, (int)blockIdx.x);
 }
+
+// ------------------------------------------------------------------------------------------
+// The same search for SEVERAL trees per launch (lqrrt_connect_search_multi; connect_goals).  A search leaves most of the chip idle
+// once its first chain has reached the goal and the early stop prunes the rest: the searches of a fleet's trees run side by side in
+// ONE launch.  As in k_refine_search_multi a workgroup finds its engine from the ascending prefix table of workgroup counts in the
+// arguments (multi_engine_of) and reads P / g / r / tv from that engine's device-resident EngineProto; what belongs to the call --
+// the candidate ids, the depth table, count, tries, H, the goal and where the winner goes -- is a ConnectDesc per engine in device
+// memory.  Every engine has its OWN best key: the early stop prunes within one tree only, so each winner is the one the engine's
+// own launch finds, whatever the scheduling.  The batched commit is k_refine_commit_multi (a RefineDesc per winner: plan = [v],
+// prefix = [depth[v]], P = 1, i = j = 0).
+struct ConnectDesc {
+    ConnectArgs a;
+    unsigned long long* best;     // the engine's key
+};
+
+// *p for data that nothing writes while the kernel runs (the host wrote it before the launch), read through the CONSTANT address
+// space.  connect_search_body polls the best key with an atomic load, and behind an atomic load the compiler takes every later read
+// of ordinary global memory for clobbered: the body's reads of P / g / r / tv -- wave-uniform, scalar loads in the solo kernel, whose
+// arguments are constant by construction -- turn into vector loads whose results sit in VGPRs (DoubleIntegratorT<6>: 256 VGPRs + 2
+// AGPRs and one wavefront per SIMD instead of two).  A read of the constant address space stays a scalar load wherever it stands.
+// The detour through an integer keeps the address-space inference from folding the cast back into the global pointer it came from.
+template <class T>
+__device__ __forceinline__ const T& launch_constant(const T* p) {
+    return *(const T*)(const __attribute__((address_space(4))) T*)(unsigned long long)p;
+}
+
+// Grid = the engines' candidate counts back to back.  Dynamic LDS: the largest refine_lds_bytes of the call.
+template <class S>
+__global__ __launch_bounds__(64) void k_connect_search_multi(ProtoTable pt, const ConnectDesc* __restrict__ ds, RetainGrid gr) {
+    extern __shared__ double geo_lds[];
+    const int e = multi_engine_of(gr.block0, gr.n, (int)blockIdx.x);
+    const ConnectDesc& d = launch_constant(ds + e);
+    const EngineProto& p = launch_constant(pt.p[e]);
+    connect_search_body<S>(p.P, p.g, p.r, p.tv, d.a, d.best, geo_lds, (int)blockIdx.x - gr.block0[e]);
+}

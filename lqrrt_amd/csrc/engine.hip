@@ -86,7 +86,7 @@ static int fail(int code, const char* fmt, ...) {
 #include "engine_multi.hpp"       // ABI: engine_extend_multi (several engines in lock step, two launches per tick)
 #include "engine_retain.hpp"      // ABI: tree_retain (Planner.replan)
 #include "engine_refine.hpp"      // ABI: refine_search / refine_commit (Planner.refine_plan; + _multi: retain_grid)
-#include "engine_connect.hpp"     // ABI: connect_search / connect_commit (Planner.connect_goal: goal chains from every tree node)
+#include "engine_connect.hpp"     // ABI: connect_search / connect_commit (Planner.connect_goal: goal chains from every tree node; + _multi)
 
 // --------------------------------------------------------------------------------------------
 // Shader clock and issue rate, measured (bench.py reports them next to every latency-bound figure; tools/micro/clock.hip is

@@ -8,7 +8,8 @@
 //   k_tree_root / k_append   <- Tree.__init__ / Tree.add_node             tree.py:50-96
 //   k_decide                 (build-only: exact-mode wave validation, see engine.hip)
 //   k_refine_search / _commit (build-only: Planner.refine_plan, chains of k_steer's rollout over a found plan; refine.hpp)
-//   k_connect_search         (build-only: Planner.connect_goal, the same chains from every node of the tree to the goal; connect.hpp)
+//   k_connect_search (+ _multi) (build-only: Planner.connect_goal / connect_goals, the same chains from every node of the tree to
+//                            the goal; connect.hpp)
 //
 // Execution model choices (MI355X; DESIGN.md section 4 has the measurements):
 //   * NN scan: one lane = one sample, one wavefront per workgroup, grid = (64-sample groups) x (node chunks) with an
@@ -209,6 +210,6 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "multi.hpp"      // k_nn_scan_multi / k_steer_multi                         (build-only: several engines per launch)
 #include "retain.hpp"     // k_retain_*                                              (Planner.replan: re-root, re-validate, compact the tree)
 #include "refine.hpp"     // k_refine_search / k_refine_commit (+ _multi: RetainGrid) (Planner.refine_plan: shortcuts of a found plan)
-#include "connect.hpp"    // k_connect_search                                         (Planner.connect_goal: goal chains from every tree node)
+#include "connect.hpp"    // k_connect_search (+ _multi: ProtoTable, RetainGrid)      (Planner.connect_goal: goal chains from every tree node)
 
 }  // namespace lq

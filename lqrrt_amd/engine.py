@@ -535,6 +535,74 @@ class Engine(object):
                                                      self._stream()))
         return out[:k].tolist()
 
+    @staticmethod
+    def _connect_multi_args(engines, horizons, goal_tries):
+        engines = list(engines)
+        n = len(engines)
+        if n < 1:
+            raise ValueError("no engines")
+        horizons = np.ascontiguousarray([int(h) for h in horizons], dtype=np.int32)
+        tries = np.ascontiguousarray(np.broadcast_to(np.asarray(goal_tries, dtype=np.int64), (n,)), dtype=np.int32)
+        if horizons.shape != (n,):
+            raise ValueError("expected one horizon per engine")
+        handles = (C.c_void_p * n)(*[e.h for e in engines])
+        return engines, n, handles, horizons, tries
+
+    @staticmethod
+    def connect_search_multi(engines, horizons, incumbents, goal_tries=8, nodes=None):
+        """connect_search for n engines in one native call (lqrrt_connect_search_multi): the searches of all trees share one kernel
+        launch, every engine with a best key of its own.  `horizons`, `incumbents`: one per engine; `goal_tries`: one for all or one
+        per engine; `nodes`: None, or one entry per engine, each None (every node) or an id list (an empty one: no candidates).
+        Returns [(cost, node) or None] in the engines' order, each what that engine's own connect_search returns.  The engines share
+        device and model; every argument is checked before anything is launched."""
+        engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
+        inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
+        if inc.shape != (n,):
+            raise ValueError("expected one incumbent per engine")
+        node_ptrs = counts = None
+        if nodes is not None:
+            nodes = list(nodes)
+            if len(nodes) != n:
+                raise ValueError("expected one id list (or None) per engine")
+            ids = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in nodes]
+            counts = np.ascontiguousarray([0 if a is None else len(a) for a in ids], dtype=np.int32)
+            ids = [a if a is None or len(a) else np.zeros(1, dtype=np.int32) for a in ids]    # (an empty list still has an address)
+            node_ptrs = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in ids])
+        cost, node = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_connect_search_multi(handles, n, node_ptrs, None if counts is None else nat.ptr(counts), nat.ptr(tries),
+                                                       nat.ptr(horizons), nat.ptr(inc), nat.ptr(cost), nat.ptr(node),
+                                                       engines[0]._stream()))
+        return [None if node[k] < 0 else (int(cost[k]), int(node[k])) for k in range(n)]
+
+    @staticmethod
+    def connect_commit_multi(engines, nodes, horizons, goal_tries=8):
+        """connect_commit for n engines in one native call (lqrrt_connect_commit_multi): one workgroup per engine replays the goal
+        chain of its candidate nodes[k] below its own tree size (None: the engine is left out and gets []).  Returns a list of
+        new-id lists, None where the tree cannot hold the chain (that tree is unchanged; the others commit).  A chain that does not
+        reach the goal raises NativeError(E_STATE) after the other engines have committed; the error carries what they appended
+        (`results`: this list, `failed`: the indices of the engines that appended nothing for that reason)."""
+        engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
+        nodes = list(nodes)
+        if len(nodes) != n:
+            raise ValueError("expected one candidate per engine")
+        if any(v is not None and int(v) < 0 for v in nodes):
+            raise ValueError("a candidate is a node id >= 0, or None")
+        cn = np.ascontiguousarray([-1 if v is None else int(v) for v in nodes], dtype=np.int32)
+        outs = [np.empty(max(int(tries[k]), 1), dtype=np.int32) for k in range(n)]
+        out_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs])
+        caps = np.ascontiguousarray([len(a) for a in outs], dtype=np.int32)
+        counts = np.zeros(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_connect_commit_multi(handles, n, nat.ptr(cn), nat.ptr(tries), nat.ptr(horizons), out_ptrs, nat.ptr(caps),
+                                                       nat.ptr(counts), engines[0]._stream()))
+        results = [None if counts[k] < 0 else outs[k][:counts[k]].tolist() for k in range(n)]
+        bad = [k for k in range(n) if counts[k] < 0 and counts[k] != nat.E_CAPACITY]
+        if bad:
+            err = nat.NativeError(int(counts[bad[0]]), "the chain below node %d of engine %d does not reach the goal: nothing appended"
+                                  % (cn[bad[0]], bad[0]))
+            err.results, err.failed = results, bad                  # what the other engines of the call committed
+            raise err
+        return results
+
     def push_samples(self, xs):
         xs = nat.as_f64(xs)
         if xs.ndim != 2 or xs.shape[1] != self.n:

@@ -596,14 +596,11 @@ class Planner:
                                       "of the search would have to run; the device cannot call it.")
         if int(goal_tries) < 1:
             raise ValueError("goal_tries must be >= 1.")
-        run = self._refine_begin(need_goal=False)
+        run = self._connect_begin()
         if run is None:
             return False
-        if not np.array_equal(self.goal, self._grown_goal):
-            raise RuntimeError("connect_goal: the goal changed since the tree was grown; use update_plan or replan.")
         eng = self._engine
-        incumbent = self._refine_incumbent(run) if self.plan_reached_goal else 2 ** 31 - 1
-        win = eng.connect_search(run.H, incumbent, goal_tries, nodes)
+        win = eng.connect_search(run.H, self._connect_incumbent(run), goal_tries, nodes)
         if win is None:
             return False
         cost, node = win
@@ -613,13 +610,33 @@ class Planner:
             if ex.code == nat.E_CAPACITY:
                 return False
             raise
-        run.core = eng.climb(node)                                  # the plan continues below `node`, its last node
+        self._connect_accept(run, cost, node, ids, finish_on_goal)
+        return True
+
+    # The steps of a goal connection that connect_goal (one planner, its engine's own calls) and connect_goals (a fleet, batched
+    # calls) share: what is searched, what the search has to beat, what a committed winner changes.  They go through the
+    # refinement's own steps.
+    def _connect_begin(self):
+        """The connection's state (_RefineRun), or None when there is no tree of this planner on the device.  Reads only."""
+        run = self._refine_begin(need_goal=False)
+        if run is None:
+            return None
+        if not np.array_equal(self.goal, self._grown_goal):
+            raise RuntimeError("connect_goal: the goal changed since the tree was grown; use update_plan or replan.")
+        return run
+
+    def _connect_incumbent(self, run):
+        """Steps of the plan to beat; a plan that did not reach the goal is beaten by any valid chain."""
+        return self._refine_incumbent(run) if self.plan_reached_goal else 2 ** 31 - 1
+
+    def _connect_accept(self, run, cost, node, ids, finish_on_goal):
+        """A committed winner: the plan is climb(node) + the appended nodes, and it reaches the goal."""
+        run.core = self._engine.climb(node)                         # the plan continues below `node`, its last node
         self._refine_accept(run, cost, len(run.core) - 1, ids)
         if finish_on_goal is not None:
             run.finish = bool(finish_on_goal)
         self.plan_reached_goal = True
         self._refine_end(run)
-        return True
 
     def _in_goal(self, x):
         """True if x lies strictly inside the goal box (planner.py:442-447)."""
@@ -1028,4 +1045,74 @@ def refine_plans(planners, max_rounds=8, goal_tries=8):
     results = [0 if run is None else p._refine_end(run) for p, run in zip(planners, runs)]
     if error is not None:
         raise error
+    return results
+
+
+def connect_goals(planners, goal_tries=8, nodes=None, finish_on_goal=None):
+    """
+    connect_goal for a fleet: every planner gets exactly what its own connect_goal(goal_tries, nodes[k], finish_on_goal) gives it --
+    node_seq, x_seq, u_seq, t_seq, T, plan_reached_goal, the appended tree nodes, the interpolators, a finish_on_goal node dropped
+    and steered again -- but the native calls are shared.  The planners of one (device, native system type) form a group; a group
+    makes ONE search call over its trees (Engine.connect_search_multi: every tree with a best key of its own, so each winner is the
+    one the planner's own search finds) and ONE commit call over those with a winner (Engine.connect_commit_multi), in slices of 128.
+    `nodes`: None, or one entry per planner, each None (every node) or an id list.  A planner with no tree of its own on the device
+    (where connect_goal returns False at once) takes part in no launch; one whose tree cannot hold the chain gets False and is
+    unchanged.  Returns the list of bools.
+
+    Refused with ValueError for EVERY planner before any is touched: a planner that appears twice, an object that is not a Planner,
+    a callback-mode planner, a tree that holds hand-added host nodes, a goal changed since the tree was grown, goal_tries < 1, a
+    `nodes` sequence of the wrong length.  If a native call fails, the planners that did commit adopt their plans -- those of the
+    failing commit call included -- then the error is raised.
+    """
+    planners = list(planners)
+    if int(goal_tries) < 1:
+        raise ValueError("goal_tries must be >= 1.")
+    if nodes is not None:
+        nodes = list(nodes)
+        if len(nodes) != len(planners):
+            raise ValueError("connect_goals: expected one id list (or None) per planner.")
+    if not planners:
+        return []
+    if len(set(id(p) for p in planners)) != len(planners):
+        raise ValueError("connect_goals: a planner appears twice.")
+    for p in planners:
+        if not isinstance(p, Planner):
+            raise ValueError("connect_goals: expected Planner objects.")
+        if p.callback_mode:                                         # (as the last set_system left it, as in connect_goal)
+            raise ValueError("connect_goals: planners whose plugins are Python callables cannot be searched (the device cannot call them).")
+    runs = []
+    for p in planners:
+        try:
+            runs.append(p._connect_begin())
+        except RuntimeError as ex:
+            raise ValueError(str(ex).replace("refine_plan:", "connect_goals:").replace("connect_goal:", "connect_goals:"))
+    results = [False] * len(planners)
+    groups = {}
+    for k, (p, run) in enumerate(zip(planners, runs)):
+        if run is not None:
+            groups.setdefault((p.device, type(p.system)), []).append(k)
+    for g in sorted(groups, key=lambda g: groups[g][0]):
+        for first in range(0, len(groups[g]), 128):                 # (a native call takes at most 128 engines)
+            mine = groups[g][first:first + 128]
+            wins = Engine.connect_search_multi([planners[k]._engine for k in mine], [runs[k].H for k in mine],
+                                               [planners[k]._connect_incumbent(runs[k]) for k in mine], goal_tries,
+                                               None if nodes is None else [nodes[k] for k in mine])
+            winners = [(k, w) for k, w in zip(mine, wins) if w is not None]
+            if not winners:
+                continue
+            failed = None
+            try:
+                new = Engine.connect_commit_multi([planners[k]._engine for k, _ in winners], [w[1] for _, w in winners],
+                                                  [runs[k].H for k, _ in winners], goal_tries)
+            except nat.NativeError as ex:
+                if getattr(ex, "results", None) is None:
+                    raise
+                new, failed = ex.results, ex                        # the other engines of the call did commit: their plans follow
+            for (k, w), ids in zip(winners, new):
+                if ids is None:                                     # capacity (or a failed chain): this planner keeps what it has
+                    continue
+                planners[k]._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
+                results[k] = True
+            if failed is not None:
+                raise failed
     return results

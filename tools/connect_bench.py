@@ -10,6 +10,15 @@ timed in the same process for scale.
 
     python tools/connect_bench.py [--reps 3] [--nodes 100000] [--out DIR]   ->  one JSON line per case; DIR/connect_bench.jsonl
     python tools/connect_bench.py --once                                     ->  one untimed search per case (for a kernel trace)
+
+--fleet N[,N...]: the calls for several trees instead (lqrrt_amd.connect_goals: Engine.connect_search_multi + connect_commit_multi).
+The boat_advanced_10k fixture is loaded into N engines, once cut at 3308 nodes (no incumbent) and once whole (the plan's cost as
+incumbent), and ONE batched search plus ONE batched commit are timed against the loop of the one-tree calls over identically loaded
+twins, in the same process: host wall clock, the trees loaded afresh (untimed) before every repetition, warmed, median of `--reps`
+with the lowest and the highest.
+
+    python tools/connect_bench.py --fleet 4,16,64 [--reps 3] [--out DIR]     ->  one JSON line per case; DIR/connect_multi_bench.jsonl
+    python tools/connect_bench.py --fleet 16 --once                          ->  one untimed pass of both (for a kernel trace)
 """
 import argparse
 import json
@@ -95,6 +104,68 @@ def run_fixture(reps, once):
     return rows
 
 
+def run_fleet(sizes, reps, once):
+    s, g = cr.case("boat_advanced_10k")
+    H = cr.horizon_of(s, g)
+    rows = []
+    for label, size in (("boat_advanced_10k prefix", cr.first_goal_node(s, g)), ("boat_advanced_10k full", None)):
+        incumbent = cr.NO_INCUMBENT if size is not None else cr.from_fixture(s, g).cost([int(v) for v in g["node_seq"]])
+        N = len(g["state"]) if size is None else size
+        el = np.array(g["edge_len"][:N], dtype=np.int32)
+        el[0] = 1
+        pool = {}
+
+        def load(eng):
+            eng.tree_load(g["state"][:N], g["K"][:N], g["pID"][:N], edge_len=el)
+
+        def batched(engines):
+            n = len(engines)
+            wins = Engine.connect_search_multi(engines, [H] * n, [incumbent] * n)
+            ids = Engine.connect_commit_multi(engines, [None if w is None else w[1] for w in wins], [H] * n)
+            return wins, ids
+
+        def loop(engines):
+            wins = [e.connect_search(H, incumbent) for e in engines]
+            ids = [[] if w is None else e.connect_commit(w[1], H) for e, w in zip(engines, wins)]
+            return wins, ids
+
+        for n in sizes:
+            while len(pool) < 2 * n:
+                pool[len(pool)] = fixture_engine(s, g, size)
+            fleet, twins = [pool[k] for k in range(n)], [pool[n + k] for k in range(n)]
+            if once:
+                batched(fleet)
+                loop(twins)
+                for e in fleet + twins:
+                    load(e)
+                continue
+            out, ts = {}, {}
+            for name, fn, engines in (("batched", batched, fleet), ("loop", loop, twins)):
+                ts[name] = []
+                for rep in range(reps + 1):                       # (the first pass warms up and is not counted)
+                    for e in engines:
+                        load(e)
+                    t0 = time.perf_counter()
+                    out[name] = fn(engines)
+                    if rep:
+                        ts[name].append(1e3 * (time.perf_counter() - t0))
+            assert out["batched"] == out["loop"] and len(set(out["loop"][0])) == 1, (label, n)
+            for a, b in zip(fleet, twins):                          # the same trees, whichever way
+                assert a.size == b.size and np.array_equal(a.states(N, a.size - N), b.states(N, b.size - N))
+            med = {k: float(np.median(v)) for k, v in ts.items()}
+            rows.append(dict(case=label, engines=n, nodes=N, incumbent=None if incumbent == cr.NO_INCUMBENT else int(incumbent),
+                             winner=out["loop"][0][0], appended=len(out["loop"][1][0]),
+                             batched_ms=round(med["batched"], 3), batched_ms_min=round(min(ts["batched"]), 3),
+                             batched_ms_max=round(max(ts["batched"]), 3), loop_ms=round(med["loop"], 3),
+                             loop_ms_min=round(min(ts["loop"]), 3), loop_ms_max=round(max(ts["loop"]), 3),
+                             batched_ms_per_tree=round(med["batched"] / n, 4), loop_ms_per_tree=round(med["loop"] / n, 4),
+                             loop_over_batched=round(med["loop"] / med["batched"], 2)))
+            print("fleet: " + json.dumps(rows[-1]), file=sys.stderr, flush=True)
+        for e in pool.values():
+            e.close()
+    return rows
+
+
 def run_native(max_nodes, reps, once):
     s = lqrrt_amd.systems.BoatAdvanced(0)
     cons = lqrrt_amd.Constraints(s.nstates, s.ncontrols, s.goal_buffer, s.is_feasible)
@@ -125,17 +196,21 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--nodes", type=int, default=100000, help="size of the natively grown tree (0: leave it out)")
     ap.add_argument("--once", action="store_true", help="one untimed search per case, no reference (for a kernel trace)")
+    ap.add_argument("--fleet", default=None, help="engines per call, e.g. 4,16,64: time the batched calls against the loop of solo calls instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    rows = run_fixture(a.reps, a.once)
-    if a.nodes > 0:
-        rows += run_native(a.nodes, a.reps, a.once)
+    if a.fleet:
+        rows, name = run_fleet([int(v) for v in a.fleet.split(",")], a.reps, a.once), "connect_multi_bench.jsonl"
+    else:
+        rows, name = run_fixture(a.reps, a.once), "connect_bench.jsonl"
+        if a.nodes > 0:
+            rows += run_native(a.nodes, a.reps, a.once)
     rows = [r for r in rows if r is not None]
     for r in rows:
         print(json.dumps(r), flush=True)
     if a.out and rows:
         os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "connect_bench.jsonl"), "w") as f:
+        with open(os.path.join(a.out, name), "w") as f:
             f.write("".join(json.dumps(r) + "\n" for r in rows))
 
 
