@@ -68,6 +68,15 @@ static size_t geo_lds_bytes(const lqrrt_engine* e) {
     return e->geo.oc ? sizeof(double) * ((size_t)2 * e->geo.V + (size_t)4 * e->geo.O) : 0;
 }
 
+// The circle model stages 8 (2V + 4O) bytes per workgroup (the steer launch: beside its edge history) and nothing bounds O: refuse
+// what the device cannot give a workgroup before anything is launched.
+static int lds_fits(const lqrrt_engine* e, size_t bytes, const char* what) {
+    if (e->lds_limit && bytes > e->lds_limit)
+        return fail(LQRRT_E_ARG, "%s needs %zu bytes of LDS per workgroup (hull points and circle table: 8 (2 V + 4 O) bytes, V = %d, O = %d), "
+                    "the device's limit is %zu: fewer obstacles or hull points", what, bytes, e->geo.V, e->geo.O, e->lds_limit);
+    return 0;
+}
+
 static int use_device(lqrrt_engine* e) {
     HIPCHK(hipSetDevice(e->device));
     return 0;
@@ -349,6 +358,7 @@ static int launch_steer(lqrrt_engine* e, const double* xs, const int* list, int 
     if (round) ra = *round;
     // (+ cos/sin of every recorded state: the two-wavefront rollout of the boats keeps them with the history)
     const size_t lds = (size_t)e->H * (e->n + e->m + 2 * std::max(e->nw, 1)) * sizeof(double) + geo_lds_bytes(e);
+    TRY(lds_fits(e, lds, "the steer launch"));
     SteerFuse f;
     memset(&f, 0, sizeof f);
     if (fuse) f = *fuse;

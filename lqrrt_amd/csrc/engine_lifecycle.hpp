@@ -125,6 +125,7 @@ extern "C" int lqrrt_engine_create(const lqrrt_system_desc* sys, int device, int
     lqrrt_engine* e = new lqrrt_engine();
     g_dalloc_bytes = 0;
     e->device = device; e->model = sys->model; e->n = n; e->m = m; e->nw = nw;
+    e->lds_limit = prop.sharedMemPerBlock;
     e->cap = ((capacity + 63) / 64) * 64; e->maxW = max_wave; e->H = 1;
     memset(&e->P, 0, sizeof e->P);
     memcpy(e->P.p, sys->params, sizeof(double) * sys->n_params);

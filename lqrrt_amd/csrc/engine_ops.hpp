@@ -8,6 +8,7 @@ extern "C" int lqrrt_feasible_batch(lqrrt_engine* e, const double* x, const doub
     if (e && B == 0) return 0;
     if (!e || !x || !ok || B < 0) return fail(LQRRT_E_ARG, "bad argument");
     if (!B) return 0;
+    TRY(lds_fits(e, geo_lds_bytes(e), "feasible_batch"));
     TRY(use_device(e));
     DISPATCH(e, hipLaunchKernelGGL((k_feasible_batch<S>), dim3(B), dim3(64), geo_lds_bytes(e), (hipStream_t)stream, e->P, e->geo, x, u, B, ok));
     HIPCHK(hipGetLastError());
@@ -143,6 +144,7 @@ extern "C" int lqrrt_steer_force(lqrrt_engine* e, int parent, const double* xtar
     if (!e || !xtar_dev || !len_dev || !xseq_dev || !useq_dev || max_steps < 1) return fail(LQRRT_E_ARG, "bad argument");
     if (!e->has_res) return fail(LQRRT_E_STATE, "set_resolution first");
     TRY(range_ok(e, parent, 1));
+    TRY(lds_fits(e, geo_lds_bytes(e), "steer_force"));
     TRY(use_device(e));
     DISPATCH(e, hipLaunchKernelGGL((k_steer_force<S>), dim3(1), dim3(64), geo_lds_bytes(e), (hipStream_t)stream, e->P, e->geo,
                                    e->res, e->tv, parent, xtar_dev, max_steps, rtol, atol, len_dev, xseq_dev, useq_dev));

@@ -45,6 +45,7 @@ static int retain_run(lqrrt_engine* e, int root, int revalidate, lqrrt_retain_st
     const int N = e->N, n = e->n, m = e->m, H = e->H;
     const int nblocks = (N + RETAIN_BLOCK - 1) / RETAIN_BLOCK;
     const size_t words = (size_t)e->cap / 64 + 1;
+    if (revalidate) TRY(lds_fits(e, geo_lds_bytes(e), "the retain check"));
     // ---- small scratch, carved out of one allocation
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };

@@ -83,6 +83,7 @@ static int refill_ahead(lqrrt_engine* e) {
         memcpy(e->h_cand_pin + (size_t)e->rf_pos * n, e->pregen.data() + (size_t)e->rf_pos * n, sizeof(double) * (size_t)(end - e->rf_pos) * n);
         e->rf_pos = end;
         if (end < CH) return 0;
+        TRY(lds_fits(e, geo_lds_bytes(e), "the sample refill"));
         HIPCHK(hipMemcpyAsync(e->d_cand2, e->h_cand_pin, sizeof(double) * (size_t)CH * n, hipMemcpyHostToDevice, e->rf_stream));
         DISPATCH(e, hipLaunchKernelGGL((k_feasible_batch<S>), dim3(CH), dim3(64), geo_lds_bytes(e), e->rf_stream, e->P, e->geo, e->d_cand2, nullptr, CH, e->d_flags2));
         HIPCHK(hipGetLastError());
@@ -167,6 +168,7 @@ static int ensure_samples(lqrrt_engine* e, int64_t need_end, hipStream_t st) {
     if (!e->has_goal) return fail(LQRRT_E_STATE, "no goal set");
     const int n = e->n;
     if (e->d_pool_count > 0 && e->cursor >= e->d_pool_base && need_end <= e->d_pool_base + e->d_pool_count) return 0;
+    TRY(lds_fits(e, geo_lds_bytes(e), "the sample refill"));
     // drop consumed samples from the host pool
     if (e->cursor > e->pool_base) {
         const int64_t drop = std::min<int64_t>(e->cursor - e->pool_base, (int64_t)e->pool_rows_end.size());

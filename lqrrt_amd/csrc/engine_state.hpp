@@ -43,6 +43,7 @@ struct EvPair { hipEvent_t a, b; double bytes; int kind; };
 
 struct lqrrt_engine {
     int device = 0;
+    size_t lds_limit = 0;         // the device's sharedMemPerBlock: no launch may ask for more dynamic LDS (lds_fits)
     int model = 0, n = 0, m = 0, nw = 0;
     int cap = 0, maxW = 0, H = 0;
     // LQRRT_MODEL_GENERIC (engine_generic.hpp): no plugins compiled in -- node table, ignore set and nearest-neighbour stage only

@@ -53,7 +53,7 @@ struct Geo {
     const unsigned char* ogc;
     int ogc_rows, ogc_cols, og_lds;      // og_lds: the hull points fit in LDS next to the edge history
     double og_reach;
-    double og_bb[4];                     // body-frame bounding box of the hull points: xmin, xmax, ymin, ymax (inflated)
+    double og_bb[4];                     // body-frame bounding box of the hull points: xmin, xmax, ymin, ymax (raw; grid_hits adds its own margin)
     double hbb[4];                       // the same box, padded, for the circle sweep's cull (hull_hits)
 };
 constexpr int OG_COARSE_SHIFT = 3;
@@ -174,7 +174,9 @@ __device__ __forceinline__ bool grid_hits(const Geo& g, const GeoL& gl, double p
             const int fx0 = (int)(g.og_cpm * ((px + wx_lo - m) - g.og_ox)) - 1, fx1 = (int)(g.og_cpm * ((px + wx_hi + m) - g.og_ox)) + 1;
             const int fy0 = (int)(g.og_cpm * ((py + wy_lo - m) - g.og_oy)) - 1, fy1 = (int)(g.og_cpm * ((py + wy_hi + m) - g.og_oy)) + 1;
             const int fnx = fx1 - fx0 + 1, fcells = fnx * (fy1 - fy0 + 1);
-            if (fcells <= 1024) {            // (inside the map: the reach box is, and this box lies within it)
+            // The corners of this box need not be hull points (a disc, a diamond, a pointed bow): rotated, it can stick out of
+            // the reach box by up to (sqrt 2 - 1) reach, and so out of the map.  Read it only where it lies inside the map.
+            if (fcells <= 1024 && fx0 >= 0 && fy0 >= 0 && fx1 < g.og_cols && fy1 < g.og_rows) {
                 bool focc = false;
                 for (int q = lane; q < fcells; q += 64) {
                     const int r = q / fnx, cc = q - r * fnx;
@@ -200,11 +202,14 @@ __device__ __forceinline__ bool grid_hits(const Geo& g, const GeoL& gl, double p
             const double bx = gl.vps[vv], by = gl.vps[g.V + vv];
             const double vx = px + (c * bx + ms * by);
             const double vy = py + (s * bx + c * by);
-            long long ix = (long long)(g.og_cpm * (vx - g.og_ox));
-            long long iy = (long long)(g.og_cpm * (vy - g.og_oy));
+            const double fx = g.og_cpm * (vx - g.og_ox), fy = g.og_cpm * (vy - g.og_oy);
+            // a non-finite coordinate, or one beyond the int64 range, is outside the map (the cast is undefined for it)
+            const bool wild = !(fabs(fx) < 0x1p63) || !(fabs(fy) < 0x1p63);
+            long long ix = (long long)fx;
+            long long iy = (long long)fy;
             if (ix < 0) ix += g.og_cols;
             if (iy < 0) iy += g.og_rows;
-            oob[k] = ix < 0 || ix >= g.og_cols || iy < 0 || iy >= g.og_rows;
+            oob[k] = wild || ix < 0 || ix >= g.og_cols || iy < 0 || iy >= g.og_rows;
             cell[k] = oob[k] ? 0 : iy * g.og_cols + ix;
         }
         signed char val[8];

@@ -143,8 +143,10 @@ static int grid_hits(const orc* o, double px, double py, double c, double s) {
     for (int v = 0; v < o->V; ++v) {
         const double bx = o->vps[v], by = o->vps[o->V + v];
         const double vx = px + (c * bx + ms * by), vy = py + (s * bx + c * by);
-        long long ix = (long long)(o->og_cpm * (vx - o->og_ox));      /* .astype(np.int64): truncation */
-        long long iy = (long long)(o->og_cpm * (vy - o->og_oy));
+        const double fx = o->og_cpm * (vx - o->og_ox), fy = o->og_cpm * (vy - o->og_oy);
+        if (!(fabs(fx) < 0x1p63) || !(fabs(fy) < 0x1p63)) return 1;   /* non-finite or beyond int64: outside the map (the cast is undefined) */
+        long long ix = (long long)fx;                                  /* .astype(np.int64): truncation */
+        long long iy = (long long)fy;
         if (ix < 0) ix += o->og_cols;                                  /* numpy: negative indices wrap once */
         if (iy < 0) iy += o->og_rows;
         if (ix < 0 || ix >= o->og_cols || iy < 0 || iy >= o->og_rows) return 1;   /* IndexError -> infeasible */
