@@ -465,6 +465,35 @@ int lqrrt_connect_search(lqrrt_engine* e, const int32_t* nodes_host, int count, 
 int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, int32_t* ids_out, int cap_ids,
                          void* stream);
 
+/* Tree-wide goal chains through waypoints (Planner.connect_via; not in the reference): lqrrt_connect_search's question with a
+ * caller's list of states between the tree and the goal -- the rest of an older plan that the tree no longer holds, the path of a
+ * coarser planner.  waypoints_host [Q][n] doubles, Q >= 0 (NULL allowed when Q = 0); a waypoint need be neither a tree node nor a
+ * feasible state.  A candidate is a pair (v, j), 0 <= j <= Q: v every node (nodes_host = NULL; count is then ignored) or one of
+ * nodes_host [count], STRICTLY ASCENDING.  It starts at v's state and gain at cost depth[v]; its targets are w_j .. w_{Q-1} in order
+ * and then the goal up to goal_tries >= 1 times, one edge per target as in lqrrt_refine_search.  An empty edge adds nothing and the
+ * chain goes on to its next target.  After every non-empty edge, a waypoint's included, the chain ends valid if its end lies
+ * strictly inside the goal box; when the targets run out first it is invalid.  j = Q is lqrrt_connect_search's candidate, and with
+ * Q = 0 the two calls give the same result bit for bit.  A chain does not steer round an obstacle that blocks it: an infeasible
+ * rollout is cut (FPR) and the chain goes on from where the cut left it.
+ *
+ * lqrrt_connect_via_search: the valid candidate of smallest (cost, node id, j) with cost < incumbent -> *cost, *node_out, *j_out;
+ * none: *cost = incumbent, *node_out = *j_out = -1.  Every argument is checked before anything is written or launched;
+ * LQRRT_E_ARG also for an id list that is not strictly ascending, a waypoint that is not finite, count (Q + 1) candidates of 64
+ * threads beyond one launch (2^32 - 1 threads), and a deepest candidate whose depth plus (Q + goal_tries) horizon_iters leaves
+ * 32-bit step counts.  One launch, one wavefront per candidate, with lqrrt_connect_search's early stop; synchronous.  The depth
+ * table, the id list, the waypoints and the key go up in one copy into the scratch of lqrrt_connect_search (8 Q n bytes more),
+ * which is not part of lqrrt_engine_footprint. */
+int lqrrt_connect_via_search(lqrrt_engine* e, const int32_t* nodes_host, int count, const double* waypoints_host, int Q,
+                             int goal_tries, int horizon_iters, int64_t incumbent, int64_t* cost, int32_t* node_out,
+                             int32_t* j_out, void* stream);
+
+/* lqrrt_connect_via_commit: replays the chain of candidate (node, j) over the same waypoints and appends its non-empty edges to the
+ * tree as a parent chain below `node`, exactly as lqrrt_connect_commit does.  ids_out [cap_ids >= Q - j + goal_tries] receives the
+ * new ids; returns their count.  LQRRT_E_CAPACITY when the tree cannot hold the chain, LQRRT_E_STATE when the chain does not reach
+ * the goal: the tree is then unchanged.  Synchronous. */
+int lqrrt_connect_via_commit(lqrrt_engine* e, int node, int j, const double* waypoints_host, int Q, int goal_tries,
+                             int horizon_iters, int32_t* ids_out, int cap_ids, void* stream);
+
 /* The two calls above for n engines at once (connect_goals), with the conventions of lqrrt_refine_*_multi: horizon, goal tries,
  * goal box and tree size may differ between the engines, which share the device and the model (Riccati systems included); no
  * engine appears twice, n <= 128.  EVERY argument of EVERY engine is checked with the rules of the one-engine calls before

@@ -87,6 +87,7 @@ static int fail(int code, const char* fmt, ...) {
 #include "engine_retain.hpp"      // ABI: tree_retain (Planner.replan)
 #include "engine_refine.hpp"      // ABI: refine_search / refine_commit (Planner.refine_plan; + _multi: retain_grid)
 #include "engine_connect.hpp"     // ABI: connect_search / connect_commit (Planner.connect_goal: goal chains from every tree node; + _multi)
+#include "engine_connect_via.hpp" // ABI: connect_via_search / connect_via_commit (Planner.connect_via: goal chains through waypoints)
 
 // --------------------------------------------------------------------------------------------
 // Shader clock and issue rate, measured (bench.py reports them next to every latency-bound figure; tools/micro/clock.hip is

@@ -211,5 +211,6 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "retain.hpp"     // k_retain_*                                              (Planner.replan: re-root, re-validate, compact the tree)
 #include "refine.hpp"     // k_refine_search / k_refine_commit (+ _multi: RetainGrid) (Planner.refine_plan: shortcuts of a found plan)
 #include "connect.hpp"    // k_connect_search (+ _multi: ProtoTable, RetainGrid)      (Planner.connect_goal: goal chains from every tree node)
+#include "connect_via.hpp" // k_connect_via_search / k_connect_via_commit                (Planner.connect_via: the same through a list of waypoints)
 
 }  // namespace lq

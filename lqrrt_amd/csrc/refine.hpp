@@ -182,6 +182,28 @@ __global__ __launch_bounds__(64) void k_refine_search(Params P, Geo g, Res r, Tr
     refine_search_body<S>(P, g, r, tv, a, best, geo_lds, (int)blockIdx.x);
 }
 
+// Writes the chain's current node (cur) and its edge rows (hx, hu: `len` of them) into the tree as node `id` below `parent`: state,
+// trig, K, parent, edge length, edge rows and -- when the sampler has fixed angles -- the angle errors (TreeView::werr).  Ends with
+// a barrier: the next edge overwrites the rows and the current node.  Shared by the commits of refine.hpp and connect_via.hpp.
+template <class S>
+__device__ __forceinline__ void refine_write_node(const TreeView& tv, const FixedAngles& fx, int id, int parent, int len,
+                                                  const double* hx, const double* hu, const double* cur, int lane) {
+    double* xe = tv.xedge + (size_t)id * tv.H * S::N;
+    double* ue = tv.uedge + (size_t)id * tv.H * S::M;
+    for (int q = lane; q < len * S::N; q += 64) xe[q] = hx[q];
+    for (int q = lane; q < len * S::M; q += 64) ue[q] = hu[q];
+    if (lane < S::N) tv.state[(size_t)lane * tv.cap + id] = cur[lane];
+    if (lane < 2 * S::NW) tv.trig[(size_t)lane * tv.cap + id] = cur[S::N + lane];
+    for (int q = lane; q < S::M * S::N; q += 64) tv.K[(size_t)id * S::M * S::N + q] = cur[S::N + 2 * S::NW + q];
+    if constexpr (S::NW > 0) {
+        if (fx.on && lane < S::NW)
+            tv.werr[(size_t)lane * tv.cap + id] = wrap_err(fx.t[2 * lane], fx.t[2 * lane + 1], cur[S::N + 2 * lane],
+                                                           cur[S::N + 2 * lane + 1]);
+    }
+    if (lane == 0) { tv.pID[id] = parent; tv.elen[id] = len; }
+    __syncthreads();
+}
+
 // Replays candidate (i, j) in one workgroup and appends its non-empty edges as nodes base, base + 1, ... (parent chain below
 // p_i), with state, trig, K, parent, edge length, edge rows and -- when the sampler has fixed angles -- the angle errors
 // (TreeView::werr).  out[0] = the number of nodes appended, or -1 when the chain does not fit below tv.cap (then nothing
@@ -207,23 +229,8 @@ __device__ __forceinline__ void refine_commit_body(const Params& P, const Geo& g
         if (len == 0) continue;
         const int id = base + added;
         if (id >= tv.cap) { added = -1; break; }
-        double* xe = tv.xedge + (size_t)id * tv.H * S::N;
-        double* ue = tv.uedge + (size_t)id * tv.H * S::M;
-        for (int q = lane; q < len * S::N; q += 64) xe[q] = hx[q];
-        for (int q = lane; q < len * S::M; q += 64) ue[q] = hu[q];
-        if (lane < S::N) tv.state[(size_t)lane * tv.cap + id] = cur[lane];
-        if (lane < 2 * S::NW) tv.trig[(size_t)lane * tv.cap + id] = cur[S::N + lane];
-        for (int q = lane; q < S::M * S::N; q += 64) tv.K[(size_t)id * S::M * S::N + q] = cur[S::N + 2 * S::NW + q];
-        if constexpr (S::NW > 0) {
-            if (fx.on && lane < S::NW)
-                tv.werr[(size_t)lane * tv.cap + id] = wrap_err(fx.t[2 * lane], fx.t[2 * lane + 1], cur[S::N + 2 * lane],
-                                                               cur[S::N + 2 * lane + 1]);
-        }
-        if (lane == 0) {
-            tv.pID[id] = parent; tv.elen[id] = len;
-            if (lens) lens[added] = len;
-        }
-        __syncthreads();                                         // the next edge overwrites the rows and the current node
+        if (lens && lane == 0) lens[added] = len;
+        refine_write_node<S>(tv, fx, id, parent, len, hx, hu, cur, lane);
         parent = id;
         ++added;
         cost += len;

@@ -535,6 +535,39 @@ class Engine(object):
                                                      self._stream()))
         return out[:k].tolist()
 
+    # -- goal chains through waypoints (csrc/engine_connect_via.hpp; the rule: tests/connect_via_reference.py) ---------
+    def _waypoints(self, waypoints):
+        way = np.ascontiguousarray(waypoints, dtype=np.float64)
+        if way.size == 0 and way.ndim <= 2:
+            way = way.reshape(0, self.n)                            # (no waypoints, however the caller spells it)
+        if way.ndim != 2 or way.shape[1] != self.n:
+            raise ValueError("expected waypoints of shape (Q, %d)" % self.n)
+        return way
+
+    def connect_via_search(self, waypoints, horizon_iters, incumbent, goal_tries=8, nodes=None):
+        """(cost, node, j) of the cheapest chain that starts at a tree node -- any node, or one of `nodes` --, steers toward
+        waypoints[j], waypoints[j + 1], ... and then up to `goal_tries` times toward the goal, and reaches the goal box in fewer than
+        `incumbent` steps from the root; ties to the smaller node id, then the smaller j; None when there is none
+        (lqrrt_connect_via_search).  j = len(waypoints) is connect_search's candidate.  An id list is sorted and its duplicates are
+        removed: the winner does not depend on its order."""
+        way = self._waypoints(waypoints)
+        ids = None if nodes is None else np.unique(np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1))
+        cost, node, j = C.c_int64(), C.c_int32(), C.c_int32()
+        nat.check(nat.lib().lqrrt_connect_via_search(self.h, None if ids is None else nat.ptr(ids), 0 if ids is None else len(ids),
+                                                     nat.ptr(way) if len(way) else None, len(way), int(goal_tries), int(horizon_iters),
+                                                     int(incumbent), C.byref(cost), C.byref(node), C.byref(j), self._stream()))
+        return None if node.value < 0 else (cost.value, node.value, j.value)
+
+    def connect_via_commit(self, node, j, waypoints, horizon_iters, goal_tries=8):
+        """Appends the chain of candidate (node, j) over `waypoints` below `node` (lqrrt_connect_via_commit); returns the new node
+        ids.  NativeError with code E_CAPACITY when the tree cannot hold it, E_STATE when the chain does not reach the goal (the tree
+        is then unchanged)."""
+        way = self._waypoints(waypoints)
+        out = np.empty(max(len(way) + int(goal_tries), 1), dtype=np.int32)
+        k = nat.check(nat.lib().lqrrt_connect_via_commit(self.h, int(node), int(j), nat.ptr(way) if len(way) else None, len(way),
+                                                         int(goal_tries), int(horizon_iters), nat.ptr(out), len(out), self._stream()))
+        return out[:k].tolist()
+
     @staticmethod
     def _connect_multi_args(engines, horizons, goal_tries):
         engines = list(engines)

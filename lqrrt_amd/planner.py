@@ -613,6 +613,63 @@ class Planner:
         self._connect_accept(run, cost, node, ids, finish_on_goal)
         return True
 
+    def connect_via(self, waypoints, goal_tries=8, nodes=None, finish_on_goal=None):
+        """
+        connect_goal with a list of states between the tree and the goal (not in the reference, whose `guide` argument is one state
+        for the fallback).  `waypoints` is an array [Q][nstates]: the rest of an earlier plan that this tree no longer holds
+        (plan_waypoints(), saved before replan dropped the branch or before a budget ran out on a smaller tree), or the path of a
+        coarser planner.  A waypoint need be neither a tree node nor a feasible state.  Every pair (v, j) of a tree node v (or a node
+        of the id list `nodes`) and 0 <= j <= Q is a candidate: from v's state and gain, steer toward waypoints[j], waypoints[j + 1],
+        ... and then toward the goal up to `goal_tries` times, one _steer(force_arrive=False) edge per target with the fixed horizon
+        `horizon_iters`; an empty edge is skipped; the chain ends with the first edge that ends inside the goal region.  The
+        candidate with the fewest steps from the root (ties to the smaller node id, then the smaller j) wins if it beats the
+        current plan.  j = Q is connect_goal's candidate, so the result is never longer than connect_goal's; without waypoints it
+        is connect_goal's.  The appended nodes are candidates of the next call, which may find a shorter plan still (a chain from
+        a new node may skip waypoints the first one went through).  The search is one kernel launch on the device
+        (csrc/connect_via.hpp); tests/connect_via_reference.py restates the rule.
+
+        What it cannot do: a chain does not steer round an obstacle that blocks it -- the LQR steer is cut where it becomes
+        infeasible and the next edge starts there.  After a map change the waypoints beyond a new obstacle are reached only from
+        tree nodes that already see them; the feature adds to sampling (update_plan, replan), it does not replace it.
+
+        Return value, refusals, `finish_on_goal` and plan_reached_goal are connect_goal's.  refine_plan() may follow.
+        """
+        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
+            raise NotImplementedError("connect_via: in callback mode the steer is the user's Python function, which every candidate "
+                                      "of the search would have to run; the device cannot call it.")
+        if int(goal_tries) < 1:
+            raise ValueError("goal_tries must be >= 1.")
+        way = np.ascontiguousarray(waypoints, dtype=np.float64)
+        if way.size == 0 and way.ndim <= 2:
+            way = way.reshape(0, self.nstates)
+        if way.ndim != 2 or way.shape[1] != self.nstates:
+            raise ValueError("Expected waypoints of shape (Q, %d)." % self.nstates)
+        run = self._connect_begin()
+        if run is None:
+            return False
+        eng = self._engine
+        win = eng.connect_via_search(way, run.H, self._connect_incumbent(run), goal_tries, nodes)
+        if win is None:
+            return False
+        cost, node, j = win
+        try:
+            ids = eng.connect_via_commit(node, j, way, run.H, goal_tries)
+        except nat.NativeError as ex:
+            if ex.code == nat.E_CAPACITY:
+                return False
+            raise
+        self._connect_accept(run, cost, node, ids, finish_on_goal)
+        return True
+
+    def plan_waypoints(self, start=0):
+        """The states of the plan's nodes node_seq[start:] as an array [len][nstates] -- what connect_via takes as waypoints.  Save
+        them before a replan or a new update_plan voids the node ids.  Host only; an empty array when there is no plan."""
+        seq = getattr(self, "node_seq", None)
+        if seq is None or self.tree is None:
+            return np.zeros((0, self.nstates))
+        state = np.asarray(self.tree.state, dtype=np.float64)
+        return np.array([state[v] for v in list(seq)[int(start):]], dtype=np.float64).reshape(-1, self.nstates)
+
     # The steps of a goal connection that connect_goal (one planner, its engine's own calls) and connect_goals (a fleet, batched
     # calls) share: what is searched, what the search has to beat, what a committed winner changes.  They go through the
     # refinement's own steps.

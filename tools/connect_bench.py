@@ -19,6 +19,14 @@ with the lowest and the highest.
 
     python tools/connect_bench.py --fleet 4,16,64 [--reps 3] [--out DIR]     ->  one JSON line per case; DIR/connect_multi_bench.jsonl
     python tools/connect_bench.py --fleet 16 --once                          ->  one untimed pass of both (for a kernel trace)
+
+--via: the search through waypoints instead (Planner.connect_via: Engine.connect_via_search), next to tests/connect_via_reference.py
+on the host with the same winner.  (a) the boat_advanced_10k fixture cut at 3308 nodes, the waypoints its plan's nodes beyond the
+cut; (b) scenario A of the retain tests -- boat_advanced grown to 5001 nodes, one more obstacle beside plan node 45, a retain from
+plan node 20 -- with the lost plan states as waypoints and the kept tree's best plan as incumbent; (c) case (a)'s tree without
+waypoints, next to Engine.connect_search on the same tree in the same process.
+
+    python tools/connect_bench.py --via [--reps 3] [--out DIR]               ->  one JSON line per case; DIR/connect_via_bench.jsonl
 """
 import argparse
 import json
@@ -166,6 +174,63 @@ def run_fleet(sizes, reps, once):
     return rows
 
 
+def via_case(label, eng, ref, way, H, reps, once, incumbent=cr.NO_INCUMBENT, **extra):
+    if once:
+        eng.connect_via_search(way, H, incumbent)
+        return None
+    got, t = timed(lambda: eng.connect_via_search(way, H, incumbent), reps)
+    row = dict(case=label, nodes=eng.size, waypoints=len(way), candidates=eng.size * (len(way) + 1),
+               incumbent=None if incumbent == cr.NO_INCUMBENT else int(incumbent), winner=got, device_ms=t["ms"],
+               device_ms_min=t["ms_min"], device_ms_max=t["ms_max"], **extra)
+    print("device: " + json.dumps(row), file=sys.stderr, flush=True)   # (the reference of a large search takes minutes)
+    t0 = time.perf_counter()
+    want = ref.search_via(way, incumbent=incumbent)
+    row["reference_s"] = round(time.perf_counter() - t0, 3)
+    assert (None if want is None else want[:3]) == got, (label, None if want is None else want[:3], got)
+    return row
+
+
+def run_via(reps, once):
+    import connect_via_reference as cvr
+    rows = []
+    # (a) and (c): the fixture cut off before its first goal node
+    s, g = cr.case("boat_advanced_10k")
+    size = cr.first_goal_node(s, g)
+    ref = cvr.from_fixture(s, g, size)
+    _, way = cvr.plan_states(g, size)
+    eng = fixture_engine(s, g, size)
+    rows.append(via_case("(a) boat_advanced_10k prefix, its plan beyond the cut", eng, ref, way, ref.H, reps, once))
+    none = np.zeros((0, s.nstates))
+    rows.append(via_case("(c) the same tree, no waypoints", eng, ref, none, ref.H, reps, once))
+    rows.append(search_case("(c) connect_search on the same tree", eng, ref, ref.H, reps, once, with_reference=False))
+    eng.close()
+    # (b): scenario A of tests/test_retain_gpu.py
+    s = lqrrt_amd.systems.BoatAdvanced(0)
+    kw = s.plan_kwargs
+    H = int(kw["horizon"] / kw["dt"])
+    eng = Engine(s, capacity=5000 + 2 * 256 + 8, max_wave=256)
+    eng.set_resolution(kw["dt"], kw["FPR"], H, np.abs(s.error_tol), s.goal, np.abs(s.goal_buffer))
+    space = np.array(s.sample_space, dtype=np.float64)
+    eng.set_sampler(np.mean(space, axis=1), np.diff(space).flatten(), np.array(s.goal_bias, dtype=np.float64), 10)
+    st = np.random.RandomState(1).get_state()
+    eng.set_mt19937(st[1], st[2])
+    eng.tree_reset(s.x0)
+    eng.extend(256, node_limit=5000)
+    plan = eng.climb(eng.plan_best()[0])
+    old = eng.states()
+    mid = old[plan[45]]
+    s.set_obstacles(np.vstack((np.asarray(s.obs, dtype=np.float64).reshape(-1, 3), [mid[0] + 4.0, mid[1], 1.0])))
+    eng.sync_geometry()
+    stats, old_to_new = eng.tree_retain(plan[20], revalidate=True)
+    way = old[[v for v in plan[20:] if old_to_new[v] < 0]]
+    ref = cvr.ViaConnector(s, eng.states(), eng.gains(), eng.parents(), eng.edge_lengths(), H)
+    incumbent = stats["best_steps"] if stats["goal_hits"] else cr.NO_INCUMBENT
+    rows.append(via_case("(b) retain scenario A, the lost plan states", eng, ref, way, H, reps, once, incumbent=incumbent,
+                         kept=stats["kept"]))
+    eng.close()
+    return rows
+
+
 def run_native(max_nodes, reps, once):
     s = lqrrt_amd.systems.BoatAdvanced(0)
     cons = lqrrt_amd.Constraints(s.nstates, s.ncontrols, s.goal_buffer, s.is_feasible)
@@ -197,9 +262,12 @@ def main():
     ap.add_argument("--nodes", type=int, default=100000, help="size of the natively grown tree (0: leave it out)")
     ap.add_argument("--once", action="store_true", help="one untimed search per case, no reference (for a kernel trace)")
     ap.add_argument("--fleet", default=None, help="engines per call, e.g. 4,16,64: time the batched calls against the loop of solo calls instead")
+    ap.add_argument("--via", action="store_true", help="time the search through waypoints (Engine.connect_via_search) instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.fleet:
+    if a.via:
+        rows, name = run_via(a.reps, a.once), "connect_via_bench.jsonl"
+    elif a.fleet:
         rows, name = run_fleet([int(v) for v in a.fleet.split(",")], a.reps, a.once), "connect_multi_bench.jsonl"
     else:
         rows, name = run_fixture(a.reps, a.once), "connect_bench.jsonl"
