@@ -41,7 +41,8 @@ __device__ __forceinline__ void mm(double* C, const double* A, const double* B, 
 // and a lone wavefront pays ~6 cycles per instruction whatever it does.)  The sums of an entry run in one lane in a fixed order and
 // a right-hand-side column never looks at another one, so a column gets the same bits whether it is solved alone or next to others
 // -- and the same bits as the entry-per-lane forms gave: same pivots, same quotient, same multiply, same subtraction
-// (tools/dare_ab.sh compares two builds bit for bit; oracle/lqrrt_oracle.c restates the elimination sequentially).
+// (tools/dare_ab.sh compares two builds bit for bit; oracle/lqrrt_oracle.c restates the elimination sequentially -- dsolve, reached on
+// its own through orc_dare_solve -- and so does tests/dare_reference.py, which also logs every exchange and every tie).
 // On return the RHS columns hold W^-1 RHS (the W columns hold the identity).
 __device__ __forceinline__ double readlane_f64(double v, int l) {        // l wave-uniform
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
@@ -156,7 +157,8 @@ struct DareLds {
 // The elimination of [I + G H | A_k | G] is the first wavefront's alone (gj_columns: one column per lane, 3 n lanes; round 5 -- until
 // then it was done four times side by side with one ENTRY per lane, ~2/3 of an iteration's instructions).  Same entries, same sums,
 // same order in both sizes: lqrrt_lqr_dare_batch and the per-sample S table (64 threads) and the rollouts (256) produce the same
-// bits, asserted on the GPU (tests/test_dare_gpu.py).
+// bits, asserted on the GPU (tests/test_dare_gpu.py test_rollout_gain_operator_and_solver_give_the_same_bits for the rollouts and
+// lqrrt_gain_batch; tests/test_nn_scan_gpu.py for the per-sample S table).
 template <class S, int NT = 64>
 __device__ __forceinline__ int dare_lqr(const double* P, const double* x0, const double* u0, const double* Qd, const double* Rd,
                                         double dt, double eps, int max_iter, double tol, DareLds<S::N, S::M>& L, int tid) {

@@ -372,22 +372,26 @@ class Engine(object):
         nat.check(nat.lib().lqrrt_erf_batch(self.h, dg.data_ptr(), dx.data_ptr(), B, e.data_ptr(), self._stream()))
         return e.cpu().numpy()
 
-    def lqr_dare_batch(self, x, u, Q, R, eps=1e-6):
-        """(S, K, A, B, iterations) of the finite-difference-linearised DARE at every (x[i], u[i])."""
+    def lqr_dare_batch(self, x, u, Q, R, eps=1e-6, outputs=("S", "K", "A", "B", "it")):
+        """(S, K, A, B, iterations) of the finite-difference-linearised DARE at every (x[i], u[i]).  u = None: zero efforts (the
+        native call's NULL).  outputs: A, B and "it" left out of it are not computed into memory (NULL) and come back as None."""
         torch = _torch()
         Bn = len(x)
         dev = "cuda:%d" % self.device
-        dx, du = self._dev(x, (Bn, self.n)), self._dev(u, (Bn, self.m))
+        if not {"S", "K"} <= set(outputs) <= {"S", "K", "A", "B", "it"}:
+            raise ValueError("outputs: S and K, optionally A, B, it")
+        dx = self._dev(x, (Bn, self.n))
+        du = self._dev(u, (Bn, self.m)) if u is not None else None
         dQ, dR = self._dev(Q, (self.n, self.n)), self._dev(R, (self.m, self.m))
         S = torch.empty((Bn, self.n, self.n), dtype=torch.float64, device=dev)
         K = torch.empty((Bn, self.m, self.n), dtype=torch.float64, device=dev)
-        A = torch.empty((Bn, self.n, self.n), dtype=torch.float64, device=dev)
-        Bm = torch.empty((Bn, self.n, self.m), dtype=torch.float64, device=dev)
-        it = torch.empty(Bn, dtype=torch.int32, device=dev)
-        nat.check(nat.lib().lqrrt_lqr_dare_batch(self.h, dx.data_ptr(), du.data_ptr(), Bn, dQ.data_ptr(), dR.data_ptr(),
-                                                 float(eps), S.data_ptr(), K.data_ptr(), A.data_ptr(), Bm.data_ptr(),
-                                                 it.data_ptr(), self._stream()))
-        return S.cpu().numpy(), K.cpu().numpy(), A.cpu().numpy(), Bm.cpu().numpy(), it.cpu().numpy()
+        A = torch.empty((Bn, self.n, self.n), dtype=torch.float64, device=dev) if "A" in outputs else None
+        Bm = torch.empty((Bn, self.n, self.m), dtype=torch.float64, device=dev) if "B" in outputs else None
+        it = torch.empty(Bn, dtype=torch.int32, device=dev) if "it" in outputs else None
+        pu, pA, pB, pit = (t.data_ptr() if t is not None else None for t in (du, A, Bm, it))
+        nat.check(nat.lib().lqrrt_lqr_dare_batch(self.h, dx.data_ptr(), pu, Bn, dQ.data_ptr(), dR.data_ptr(),
+                                                 float(eps), S.data_ptr(), K.data_ptr(), pA, pB, pit, self._stream()))
+        return tuple(t.cpu().numpy() if t is not None else None for t in (S, K, A, Bm, it))
 
     def nn_argmin(self, xs, S=None, use_ignore=True):
         torch = _torch()

@@ -37,12 +37,27 @@ def lib():
         L.orc_nearest_prefix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.orc_costs_prefix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.orc_steer_from.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.orc_dare_solve.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int] + [C.c_void_p] * 2
         _lib = L
     return _lib
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def dare_solve(A, B, Q, R, tol=1e-14, max_iter=64):
+    """(S, K, iterations) of the oracle's doubling solver alone (orc_dare_solve): what dare_lqr runs after its linearisation, for
+    any A (n x n), B (n x m), Q (n x n), R (m x m) up to the oracle's MAXN x MAXM."""
+    A, B, Q, R = _f(A), _f(B), _f(Q), _f(R)
+    n, m = B.shape
+    if A.shape != (n, n) or Q.shape != (n, n) or R.shape != (m, m):
+        raise ValueError("A (n x n), B (n x m), Q (n x n), R (m x m)")
+    S, K = np.empty((n, n)), np.empty((m, n))
+    it = lib().orc_dare_solve(n, m, _p(A), _p(B), _p(Q), _p(R), float(tol), int(max_iter), _p(S), _p(K))
+    if it < 0:
+        raise ValueError("n = %d, m = %d outside the oracle's sizes" % (n, m))
+    return S, K, it
 
 
 class _UserModel(C.Structure):

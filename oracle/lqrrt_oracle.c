@@ -196,32 +196,13 @@ static void dsolve(double* W, double* RHS, int n, int q) {     /* W X = RHS by G
 }
 /* where a Riccati problem keeps Q, R and the difference step in its parameter block (pendulum: 18 | 34 | 35; the novice
  * boat, whose lqr linearises about (x, 0) whatever u is: 19 | 55 | 64) */
-static void trig_of(const orc* o, const double* x, double* tr);
-static int dare_lqr(const orc* o, const double* x0, const double* u_in, double* S_out, double* K_out) {
+/* The solver alone, after the linearisation: S (n x n, symmetrised) and K (m x n) for A (n x n), B (n x m), Q (n x n), R (m x m),
+ * all row-major; n <= MAXN, m <= MAXM.  S or K may be NULL.  Returns the doubling iterations used (orc_dare_solve exports it:
+ * the compiled twin of tests/dare_reference.py dare_solve). */
+static int dare_solve(int n, int m, const double* A, const double* Bm, const double* Qd, const double* Rd, double tol, int max_iter,
+                      double* S_out, double* K_out) {
     enum { NN = MAXN * MAXN };
-    const int n = o->n, m = o->m;
-    const int boat = o->model == BOAT_NOV_LQR;
-    const int PLQR_Q = boat ? 19 : 18, PLQR_R = boat ? 55 : 34, PLQR_EPS = boat ? 64 : 35;
-    const double zero_u[MAXM] = {0};
-    const double* u0 = boat ? zero_u : u_in;
-    const double *Qd = o->P + PLQR_Q, *Rd = o->P + PLQR_R, eps = o->P[PLQR_EPS], dt = o->dt, tol = 1e-14;
-    double A[NN], Bm[NN], Ak[NN], G[NN], Hm[NN], W[NN], T1[NN], T2[NN], T3[NN], Rm[MAXM * MAXM], X[NN], Y[NN], Z[MAXM * MAXM];
-    for (int lane = 0; lane < n + m; ++lane) {                 /* central differences, one perturbed coordinate each */
-        double xp[MAXN], xm[MAXN], xa[MAXN], ua[MAXM], uc[MAXM], tr[4];
-        for (int sgn = 0; sgn < 2; ++sgn) {
-            for (int d = 0; d < n; ++d) xa[d] = x0[d];
-            for (int j = 0; j < m; ++j) ua[j] = u0[j];
-            const double h = sgn == 0 ? eps : -eps;
-            if (lane < n) xa[lane] += h; else ua[lane - n] += h;
-            trig_of(o, xa, tr);
-            for (int j = 0; j < m; ++j) uc[j] = ua[j];
-            step(o, xa, tr, uc, dt, sgn == 0 ? xp : xm);
-        }
-        for (int d = 0; d < n; ++d) {
-            const double v = (xp[d] - xm[d]) / (2.0 * eps);
-            if (lane < n) A[d * n + lane] = v; else Bm[d * m + (lane - n)] = v;
-        }
-    }
+    double Ak[NN], G[NN], Hm[NN], W[NN], T1[NN], T2[NN], T3[NN], Rm[MAXM * MAXM], X[NN], Y[NN], Z[MAXM * MAXM];
     for (int i = 0; i < m * m; ++i) Rm[i] = Rd[i];
     for (int i = 0; i < n * n; ++i) { Hm[i] = Qd[i]; Ak[i] = A[i]; }
     for (int i = 0; i < m * n; ++i) X[i] = Bm[(i % n) * m + (i / n)];
@@ -229,7 +210,7 @@ static int dare_lqr(const orc* o, const double* x0, const double* u_in, double* 
     dsolve(Z, X, m, n);                                         /* X = R^-1 B' */
     dmm(G, Bm, X, n, m, n, 0, 0);
     int it = 0;
-    for (; it < 64; ++it) {
+    for (; it < max_iter; ++it) {
         dmm(W, G, Hm, n, n, n, 0, 0);
         for (int i = 0; i < n; ++i) W[i * n + i] += 1.0;
         for (int i = 0; i < n * n; ++i) { T1[i] = Ak[i]; T2[i] = G[i]; T3[i] = W[i]; }
@@ -259,6 +240,34 @@ static int dare_lqr(const orc* o, const double* x0, const double* u_in, double* 
     if (S_out) memcpy(S_out, T1, sizeof(double) * n * n);
     if (K_out) memcpy(K_out, Y, sizeof(double) * m * n);
     return it;
+}
+static void trig_of(const orc* o, const double* x, double* tr);
+static int dare_lqr(const orc* o, const double* x0, const double* u_in, double* S_out, double* K_out) {
+    enum { NN = MAXN * MAXN };
+    const int n = o->n, m = o->m;
+    const int boat = o->model == BOAT_NOV_LQR;
+    const int PLQR_Q = boat ? 19 : 18, PLQR_R = boat ? 55 : 34, PLQR_EPS = boat ? 64 : 35;
+    const double zero_u[MAXM] = {0};
+    const double* u0 = boat ? zero_u : u_in;
+    const double *Qd = o->P + PLQR_Q, *Rd = o->P + PLQR_R, eps = o->P[PLQR_EPS], dt = o->dt;
+    double A[NN], Bm[NN];
+    for (int lane = 0; lane < n + m; ++lane) {                 /* central differences, one perturbed coordinate each */
+        double xp[MAXN], xm[MAXN], xa[MAXN], ua[MAXM], uc[MAXM], tr[4];
+        for (int sgn = 0; sgn < 2; ++sgn) {
+            for (int d = 0; d < n; ++d) xa[d] = x0[d];
+            for (int j = 0; j < m; ++j) ua[j] = u0[j];
+            const double h = sgn == 0 ? eps : -eps;
+            if (lane < n) xa[lane] += h; else ua[lane - n] += h;
+            trig_of(o, xa, tr);
+            for (int j = 0; j < m; ++j) uc[j] = ua[j];
+            step(o, xa, tr, uc, dt, sgn == 0 ? xp : xm);
+        }
+        for (int d = 0; d < n; ++d) {
+            const double v = (xp[d] - xm[d]) / (2.0 * eps);
+            if (lane < n) A[d * n + lane] = v; else Bm[d * m + (lane - n)] = v;
+        }
+    }
+    return dare_solve(n, m, A, Bm, Qd, Rd, 1e-14, 64, S_out, K_out);
 }
 
 static void gain(const orc* o, const double* x, const double* tr, const double* u, double* K) {
@@ -864,6 +873,11 @@ int orc_feasible(const orc* o, const double* x, const double* u) { double tr[4];
 void orc_gain(const orc* o, const double* x, const double* u, double* K) { double tr[4]; trig_of(o, x, tr); gain(o, x, tr, u, K); }
 /* (S, K, doubling iterations) of the Riccati lqr at (x, u) -- PEND_LQR and BOAT_NOV_LQR */
 int orc_lqr(const orc* o, const double* x, const double* u, double* S, double* K) { return dare_lqr(o, x, u, S, K); }
+int orc_dare_solve(int n, int m, const double* A, const double* B, const double* Q, const double* R, double tol, int max_iter,
+                   double* S, double* K) {
+    if (n < 1 || n > MAXN || m < 1 || m > MAXM || !A || !B || !Q || !R) return -1;
+    return dare_solve(n, m, A, B, Q, R, tol, max_iter, S, K);
+}
 void orc_erf(const orc* o, const double* xg, const double* x, double* e) {
     double gt[4], tr[4];
     trig_of(o, xg, gt); trig_of(o, x, tr);

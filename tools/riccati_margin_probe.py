@@ -11,32 +11,20 @@ with eps = 1e-6 and of its twin with eps = 1e-4."""
 import os
 import sys
 
-import mpmath as mp
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("oracle", "tests", ""):
     sys.path.insert(0, os.path.join(ROOT, p))
 import coracle  # noqa: E402
+from dare_reference import dare_mp  # noqa: E402
 import lqrrt_amd  # noqa: E402
 import teacher  # noqa: E402
 from systems_np import SYSTEMS  # noqa: E402
 
-mp.mp.dps = 60
-
 
 def mp_dare(A, B, Q, R):
-    A, B, Q, R = (mp.matrix(M.tolist()) for M in (A, B, Q, R))
-    n = A.rows
-    G, H, Ak, I = B * mp.inverse(R) * B.T, Q, A, mp.eye(n)
-    for _ in range(80):
-        W = mp.inverse(I + G * H)
-        A1, G1, H1 = Ak * W * Ak, G + Ak * W * G * Ak.T, H + Ak.T * H * W * Ak
-        d = max(abs(H1[i, j] - H[i, j]) for i in range(n) for j in range(n))
-        Ak, G, H = A1, G1, H1
-        if d < mp.mpf(10) ** (-45) * max(abs(H[i, j]) for i in range(n) for j in range(n)):
-            break
-    return np.array(H.tolist(), dtype=np.float64)
+    return dare_mp(A, B, Q, R, dps=60)[0]
 
 
 def np_dare(A, B, Q, R, tol=1e-14):
