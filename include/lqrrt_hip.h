@@ -517,6 +517,38 @@ int lqrrt_connect_commit_multi(lqrrt_engine** engines, int n, const int32_t* nod
                                const int32_t* horizon_iters, int32_t* const* ids_out, const int32_t* cap_ids, int32_t* counts_out,
                                void* stream);
 
+/* lqrrt_connect_via_search / lqrrt_connect_via_commit for n engines at once (connect_vias), with the conventions of the two calls
+ * above: the engines share the device and the model, no engine appears twice, n <= 128; up to 32 engines share a launch (more:
+ * consecutive chunks on `stream`, also where one launch would exceed 2^32 threads) and the call waits for the stream once.  Every
+ * engine has its OWN waypoint table waypoints[k] [Q[k]][n] (Q[k] >= 0; waypoints or waypoints[k] may be NULL where Q[k] = 0), id
+ * list, goal tries, horizon, incumbent and best key: the early stop prunes within one tree only.  EVERY argument of EVERY engine is
+ * checked with the rules of the one-engine calls before anything is written or launched: LQRRT_E_ARG for a null entry, an engine
+ * twice, mixed devices or models, more than 128 engines, Q[k] < 0 or Q[k] > 0 without a table, a waypoint that is not finite, an id
+ * list that is not strictly ascending, an incumbent out of range, counts[k] (Q[k] + 1) candidates of 64 threads beyond one launch,
+ * and a deepest candidate whose depth plus (Q[k] + goal_tries[k]) horizon_iters[k] leaves 32-bit step counts; LQRRT_E_STATE for an
+ * LQRRT_MODEL_GENERIC engine.  The device scratch behind a call (per chunk the keys, a descriptor per engine and every engine's
+ * waypoints, depth table and id list, held by the chunk's first engine) is that of lqrrt_refine_*_multi and is not part of
+ * lqrrt_engine_footprint.  Synchronous.
+ *
+ * lqrrt_connect_via_search_multi: one search launch per chunk -- per engine the result of lqrrt_connect_via_search in cost_out[k],
+ * node_out[k], j_out[k] (none: incumbents[k], -1, -1).  nodes = NULL: every node of every tree; else nodes[k] = NULL: every node
+ * of tree k, or its strictly ascending id list [counts[k]].  An engine with an empty id list takes part in no launch and has no
+ * winner. */
+int lqrrt_connect_via_search_multi(lqrrt_engine** engines, int n, const int32_t* const* nodes, const int32_t* counts,
+                                   const double* const* waypoints, const int32_t* Q, const int32_t* goal_tries,
+                                   const int32_t* horizon_iters, const int64_t* incumbents, int64_t* cost_out, int32_t* node_out,
+                                   int32_t* j_out, void* stream);
+
+/* lqrrt_connect_via_commit_multi: one commit launch per chunk, one workgroup per engine with a candidate (nodes[k], j[k]) over its
+ * own waypoints; nodes[k] = -1 leaves engine k out (counts_out[k] = 0).  ids_out[k] [cap_ids[k] >= Q[k] - j[k] + goal_tries[k]]
+ * receives engine k's new ids and counts_out[k] their number; counts_out[k] = LQRRT_E_CAPACITY when that tree cannot hold the
+ * chain, LQRRT_E_STATE when the chain does not reach the goal: that engine's tree and host mirrors are then unchanged, the others
+ * commit, and the call returns 0.  The edge lengths of every chain come back with the outputs in one copy per chunk. */
+int lqrrt_connect_via_commit_multi(lqrrt_engine** engines, int n, const int32_t* nodes /* -1: no winner */, const int32_t* j,
+                                   const double* const* waypoints, const int32_t* Q, const int32_t* goal_tries,
+                                   const int32_t* horizon_iters, int32_t* const* ids_out, const int32_t* cap_ids,
+                                   int32_t* counts_out, void* stream);
+
 /* ---------------------------------------------------------------- wave engine -------- */
 
 /* Explicit sample stream: the caller supplies the samples (a user xrand_gen function,

@@ -11,13 +11,14 @@ lqrrt_amd -- MI355X-native expansion engine behind the jnez71/lqRRT Python API.
 
 Exports mirror lqrrt/__init__.py:1-2 of the reference (Constraints, Planner) plus Tree and
 the native problem plugins (systems), update_plans (several planners through shared native calls: one GPU, many
-trees -- planner.py), refine_plans (their found plans shortened through shared calls) and connect_goals (the plans whose
-budget ran out before a goal hit connected to the goal through shared calls).  Importing works without a GPU; computing does not.
+trees -- planner.py), refine_plans (their found plans shortened through shared calls), connect_goals (the plans whose
+budget ran out before a goal hit connected to the goal through shared calls) and connect_vias (the same through each planner's own
+list of waypoints).  Importing works without a GPU; computing does not.
 """
 from .constraints import Constraints
-from .planner import Planner, update_plans, refine_plans, connect_goals
+from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias
 from .tree import Tree
 from . import systems
 from . import dare
 
-__all__ = ["Constraints", "Planner", "Tree", "systems", "dare", "update_plans", "refine_plans", "connect_goals"]
+__all__ = ["Constraints", "Planner", "Tree", "systems", "dare", "update_plans", "refine_plans", "connect_goals", "connect_vias"]

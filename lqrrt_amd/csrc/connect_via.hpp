@@ -87,11 +87,14 @@ __global__ __launch_bounds__(64) void k_connect_via_search(Params P, Geo g, Res 
 
 // Replays candidate (v, j) in one workgroup and appends its non-empty edges as nodes base, base + 1, ... (a parent chain below v)
 // through refine.hpp's node writer.  depth: depth[v].  out as in refine_commit_body: out[0] = the number of nodes appended, or -1
-// when the chain does not fit below tv.cap; out[1] = the chain's cost; out[2] = 1 when it ended in the goal box.
+// when the chain does not fit below tv.cap; out[1] = the chain's cost; out[2] = 1 when it ended in the goal box.  lens (may be
+// null), as in refine_commit_body: the appended nodes' edge lengths once more, in order, where the host finds those of a whole
+// call in one copy.
 template <class S>
 __device__ __forceinline__ void connect_via_commit_body(const Params& P, const Geo& g, const Res& r, const TreeView& tv,
                                                         const ConnectViaArgs& a, int v, int j, int depth, int base,
-                                                        const FixedAngles& fx, int* __restrict__ out, double* lds) {
+                                                        const FixedAngles& fx, int* __restrict__ out, int* __restrict__ lens,
+                                                        double* lds) {
     __shared__ GainLds<S> gl_lds;
     const int lane = threadIdx.x;
     const GeoL gl = stage_geo(g, lds, lane, 64);
@@ -107,6 +110,7 @@ __device__ __forceinline__ void connect_via_commit_body(const Params& P, const G
         if (len == 0) continue;
         const int id = base + added;
         if (id >= tv.cap) { added = -1; break; }
+        if (lens && lane == 0) lens[added] = len;
         refine_write_node<S>(tv, fx, id, parent, len, hx, hu, cur, lane);
         parent = id;
         ++added;
@@ -121,5 +125,5 @@ __global__ __launch_bounds__(64) void k_connect_via_commit(Params P, Geo g, Res 
                                                            int depth, int base, FixedAngles fx, int* __restrict__ out) {
     extern __shared__ double geo_lds[];
     if (blockIdx.x != 0) return;
-    connect_via_commit_body<S>(P, g, r, tv, a, v, j, depth, base, fx, out, geo_lds);
+    connect_via_commit_body<S>(P, g, r, tv, a, v, j, depth, base, fx, out, nullptr, geo_lds);
 }

@@ -10,6 +10,8 @@
 //   k_refine_search / _commit (build-only: Planner.refine_plan, chains of k_steer's rollout over a found plan; refine.hpp)
 //   k_connect_search (+ _multi) (build-only: Planner.connect_goal / connect_goals, the same chains from every node of the tree to
 //                            the goal; connect.hpp)
+//   k_connect_via_search / _commit (+ _multi) (build-only: Planner.connect_via / connect_vias, those chains through a caller's
+//                            waypoints; connect_via.hpp, connect_via_multi.hpp)
 //
 // Execution model choices (MI355X; DESIGN.md section 4 has the measurements):
 //   * NN scan: one lane = one sample, one wavefront per workgroup, grid = (64-sample groups) x (node chunks) with an
@@ -212,5 +214,6 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "refine.hpp"     // k_refine_search / k_refine_commit (+ _multi: RetainGrid) (Planner.refine_plan: shortcuts of a found plan)
 #include "connect.hpp"    // k_connect_search (+ _multi: ProtoTable, RetainGrid)      (Planner.connect_goal: goal chains from every tree node)
 #include "connect_via.hpp" // k_connect_via_search / k_connect_via_commit                (Planner.connect_via: the same through a list of waypoints)
+#include "connect_via_multi.hpp" // k_connect_via_search_multi / k_connect_via_commit_multi (connect_vias: several trees per launch)
 
 }  // namespace lq

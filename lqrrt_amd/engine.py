@@ -640,6 +640,79 @@ class Engine(object):
             raise err
         return results
 
+    # -- goal chains through waypoints for several trees per call (csrc/engine_connect_via_multi.hpp) ---------
+    @staticmethod
+    def _waypoints_multi(engines, waypoints):
+        """One table [Q][n] per engine (None or empty: Q = 0), the array of their addresses and their lengths."""
+        waypoints = list(waypoints)
+        if len(waypoints) != len(engines):
+            raise ValueError("expected one waypoint table (or None) per engine")
+        ways = [e._waypoints(() if w is None else w) for e, w in zip(engines, waypoints)]
+        ptrs = (C.c_void_p * len(ways))(*[w.ctypes.data if len(w) else None for w in ways])
+        return ways, ptrs, np.ascontiguousarray([len(w) for w in ways], dtype=np.int32)
+
+    @staticmethod
+    def connect_via_search_multi(engines, waypoints, horizons, incumbents, goal_tries=8, nodes=None):
+        """connect_via_search for n engines in one native call (lqrrt_connect_via_search_multi): the searches of all trees share one
+        kernel launch, every engine with its own waypoint table and a best key of its own.  `waypoints`: one entry per engine, an
+        array [Q_k][n] or None / empty (Q_k = 0: connect_search's candidates); `horizons`, `incumbents`: one per engine;
+        `goal_tries`: one for all or one per engine; `nodes`: None, or one entry per engine, each None (every node) or an id list
+        (sorted and freed of duplicates as connect_via_search does; an empty one: no candidates).  Returns [(cost, node, j) or None]
+        in the engines' order, each what that engine's own connect_via_search returns.  The engines share device and model; every
+        argument is checked before anything is launched."""
+        engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
+        ways, way_ptrs, Q = Engine._waypoints_multi(engines, waypoints)
+        inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
+        if inc.shape != (n,):
+            raise ValueError("expected one incumbent per engine")
+        node_ptrs = counts = None
+        if nodes is not None:
+            nodes = list(nodes)
+            if len(nodes) != n:
+                raise ValueError("expected one id list (or None) per engine")
+            ids = [None if v is None else np.unique(np.ascontiguousarray(v, dtype=np.int32).reshape(-1)) for v in nodes]
+            counts = np.ascontiguousarray([0 if a is None else len(a) for a in ids], dtype=np.int32)
+            ids = [a if a is None or len(a) else np.zeros(1, dtype=np.int32) for a in ids]    # (an empty list still has an address)
+            node_ptrs = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in ids])
+        cost, node, j = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_connect_via_search_multi(handles, n, node_ptrs, None if counts is None else nat.ptr(counts), way_ptrs,
+                                                           nat.ptr(Q), nat.ptr(tries), nat.ptr(horizons), nat.ptr(inc), nat.ptr(cost),
+                                                           nat.ptr(node), nat.ptr(j), engines[0]._stream()))
+        return [None if node[k] < 0 else (int(cost[k]), int(node[k]), int(j[k])) for k in range(n)]
+
+    @staticmethod
+    def connect_via_commit_multi(engines, candidates, waypoints, horizons, goal_tries=8):
+        """connect_via_commit for n engines in one native call (lqrrt_connect_via_commit_multi): one workgroup per engine replays the
+        chain of its candidate candidates[k] = (node, j) over its own waypoints below its own tree size (None: the engine is left
+        out and gets []).  Returns a list of new-id lists, None where the tree cannot hold the chain (that tree is unchanged; the
+        others commit).  A chain that does not reach the goal raises NativeError(E_STATE) after the other engines have committed; the
+        error carries what they appended (`results`: this list, `failed`: the indices of the engines that appended nothing for that
+        reason)."""
+        engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
+        ways, way_ptrs, Q = Engine._waypoints_multi(engines, waypoints)
+        candidates = list(candidates)
+        if len(candidates) != n:
+            raise ValueError("expected one candidate per engine")
+        if any(c is not None and (int(c[0]) < 0 or int(c[1]) < 0) for c in candidates):
+            raise ValueError("a candidate is a pair (node id >= 0, first waypoint >= 0), or None")
+        cn = np.ascontiguousarray([-1 if c is None else int(c[0]) for c in candidates], dtype=np.int32)
+        cj = np.ascontiguousarray([-1 if c is None else int(c[1]) for c in candidates], dtype=np.int32)
+        outs = [np.empty(max(int(Q[k]) + int(tries[k]), 1), dtype=np.int32) for k in range(n)]
+        out_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs])
+        caps = np.ascontiguousarray([len(a) for a in outs], dtype=np.int32)
+        counts = np.zeros(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_connect_via_commit_multi(handles, n, nat.ptr(cn), nat.ptr(cj), way_ptrs, nat.ptr(Q), nat.ptr(tries),
+                                                           nat.ptr(horizons), out_ptrs, nat.ptr(caps), nat.ptr(counts),
+                                                           engines[0]._stream()))
+        results = [None if counts[k] < 0 else outs[k][:counts[k]].tolist() for k in range(n)]
+        bad = [k for k in range(n) if counts[k] < 0 and counts[k] != nat.E_CAPACITY]
+        if bad:
+            err = nat.NativeError(int(counts[bad[0]]), "the chain of candidate (%d, %d) of engine %d does not reach the goal: nothing appended"
+                                  % (cn[bad[0]], cj[bad[0]], bad[0]))
+            err.results, err.failed = results, bad                  # what the other engines of the call committed
+            raise err
+        return results
+
     def push_samples(self, xs):
         xs = nat.as_f64(xs)
         if xs.ndim != 2 or xs.shape[1] != self.n:

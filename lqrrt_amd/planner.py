@@ -1105,6 +1105,88 @@ def refine_plans(planners, max_rounds=8, goal_tries=8):
     return results
 
 
+def connect_vias(planners, waypoints, goal_tries=8, nodes=None, finish_on_goal=None):
+    """
+    connect_via for a fleet: every planner gets exactly what its own connect_via(waypoints[k], goal_tries, nodes[k], finish_on_goal)
+    gives it -- node_seq, x_seq, u_seq, t_seq, T, plan_reached_goal, the appended tree nodes, the interpolators, a finish_on_goal node
+    dropped and steered again -- but the native calls are shared.  `waypoints`: one entry per planner, an array [Q_k][nstates] (the
+    rest of that planner's last plan, saved with plan_waypoints() before update_plans dropped the branch) or None / empty: that
+    planner's search is connect_goal's.  The planners of one (device, native system type) form a group; a group makes ONE search call
+    over its trees (Engine.connect_via_search_multi: every tree with its own waypoint table and a best key of its own, so each winner
+    is the one the planner's own search finds) and ONE commit call over those with a winner (Engine.connect_via_commit_multi), in
+    slices of 128.  `nodes`: None, or one entry per planner, each None (every node) or an id list.  A planner with no tree of its own
+    on the device (where connect_via returns False at once) takes part in no launch; one whose tree cannot hold the chain gets False
+    and is unchanged.  Returns the list of bools.
+
+    Refused with ValueError for EVERY planner before any is touched: everything connect_goals refuses, a `waypoints` sequence of the
+    wrong length, an array not of shape (Q, nstates).  If a native call fails, the planners that did commit adopt their plans -- those
+    of the failing commit call included -- then the error is raised.
+    """
+    planners = list(planners)
+    if int(goal_tries) < 1:
+        raise ValueError("goal_tries must be >= 1.")
+    waypoints = list(waypoints)
+    if len(waypoints) != len(planners):
+        raise ValueError("connect_vias: expected one waypoint array (or None) per planner.")
+    if nodes is not None:
+        nodes = list(nodes)
+        if len(nodes) != len(planners):
+            raise ValueError("connect_vias: expected one id list (or None) per planner.")
+    if not planners:
+        return []
+    if len(set(id(p) for p in planners)) != len(planners):
+        raise ValueError("connect_vias: a planner appears twice.")
+    for p in planners:
+        if not isinstance(p, Planner):
+            raise ValueError("connect_vias: expected Planner objects.")
+        if p.callback_mode:                                         # (as the last set_system left it, as in connect_via)
+            raise ValueError("connect_vias: planners whose plugins are Python callables cannot be searched (the device cannot call them).")
+    ways = []
+    for k, (p, w) in enumerate(zip(planners, waypoints)):
+        way = np.ascontiguousarray(() if w is None else w, dtype=np.float64)
+        if way.size == 0 and way.ndim <= 2:
+            way = way.reshape(0, p.nstates)
+        if way.ndim != 2 or way.shape[1] != p.nstates:
+            raise ValueError("connect_vias: expected waypoints of shape (Q, %d) for planner %d." % (p.nstates, k))
+        ways.append(way)
+    runs = []
+    for p in planners:
+        try:
+            runs.append(p._connect_begin())
+        except RuntimeError as ex:
+            raise ValueError(str(ex).replace("refine_plan:", "connect_vias:").replace("connect_goal:", "connect_vias:"))
+    results = [False] * len(planners)
+    groups = {}
+    for k, (p, run) in enumerate(zip(planners, runs)):
+        if run is not None:
+            groups.setdefault((p.device, type(p.system)), []).append(k)
+    for g in sorted(groups, key=lambda g: groups[g][0]):
+        for first in range(0, len(groups[g]), 128):                 # (a native call takes at most 128 engines)
+            mine = groups[g][first:first + 128]
+            wins = Engine.connect_via_search_multi([planners[k]._engine for k in mine], [ways[k] for k in mine], [runs[k].H for k in mine],
+                                                   [planners[k]._connect_incumbent(runs[k]) for k in mine], goal_tries,
+                                                   None if nodes is None else [nodes[k] for k in mine])
+            winners = [(k, w) for k, w in zip(mine, wins) if w is not None]
+            if not winners:
+                continue
+            failed = None
+            try:
+                new = Engine.connect_via_commit_multi([planners[k]._engine for k, _ in winners], [(w[1], w[2]) for _, w in winners],
+                                                      [ways[k] for k, _ in winners], [runs[k].H for k, _ in winners], goal_tries)
+            except nat.NativeError as ex:
+                if getattr(ex, "results", None) is None:
+                    raise
+                new, failed = ex.results, ex                        # the other engines of the call did commit: their plans follow
+            for (k, w), ids in zip(winners, new):
+                if ids is None:                                     # capacity (or a failed chain): this planner keeps what it has
+                    continue
+                planners[k]._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
+                results[k] = True
+            if failed is not None:
+                raise failed
+    return results
+
+
 def connect_goals(planners, goal_tries=8, nodes=None, finish_on_goal=None):
     """
     connect_goal for a fleet: every planner gets exactly what its own connect_goal(goal_tries, nodes[k], finish_on_goal) gives it --

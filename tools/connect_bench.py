@@ -27,6 +27,13 @@ plan node 20 -- with the lost plan states as waypoints and the kept tree's best 
 waypoints, next to Engine.connect_search on the same tree in the same process.
 
     python tools/connect_bench.py --via [--reps 3] [--out DIR]               ->  one JSON line per case; DIR/connect_via_bench.jsonl
+
+--via --fleet N[,N...]: the waypoint calls for several trees (lqrrt_amd.connect_vias: Engine.connect_via_search_multi +
+connect_via_commit_multi).  Case (a) -- the tree and its waypoints -- is loaded into N engines, and ONE batched search plus ONE
+batched commit are timed against the loop of the one-tree pair over identically loaded twins, in the same process: host wall clock,
+the trees loaded afresh (untimed) before every repetition, warmed, median of `--reps` with the lowest and the highest.
+
+    python tools/connect_bench.py --via --fleet 4,16 [--reps 3] [--out DIR]  ->  one JSON line per size; DIR/connect_vias_bench.jsonl
 """
 import argparse
 import json
@@ -231,6 +238,68 @@ def run_via(reps, once):
     return rows
 
 
+def run_via_fleet(sizes, reps, once):
+    import connect_via_reference as cvr
+    s, g = cr.case("boat_advanced_10k")
+    H = cr.horizon_of(s, g)
+    N = cr.first_goal_node(s, g)
+    _, way = cvr.plan_states(g, N)
+    el = np.array(g["edge_len"][:N], dtype=np.int32)
+    el[0] = 1
+    label = "(a) boat_advanced_10k prefix, its plan beyond the cut"
+    pool, rows = {}, []
+
+    def load(eng):
+        eng.tree_load(g["state"][:N], g["K"][:N], g["pID"][:N], edge_len=el)
+
+    def batched(engines):
+        n = len(engines)
+        wins = Engine.connect_via_search_multi(engines, [way] * n, [H] * n, [cr.NO_INCUMBENT] * n)
+        ids = Engine.connect_via_commit_multi(engines, [None if w is None else (w[1], w[2]) for w in wins], [way] * n, [H] * n)
+        return wins, ids
+
+    def loop(engines):
+        wins = [e.connect_via_search(way, H, cr.NO_INCUMBENT) for e in engines]
+        ids = [[] if w is None else e.connect_via_commit(w[1], w[2], way, H) for e, w in zip(engines, wins)]
+        return wins, ids
+
+    for n in sizes:
+        while len(pool) < 2 * n:
+            pool[len(pool)] = fixture_engine(s, g, N)
+        fleet, twins = [pool[k] for k in range(n)], [pool[n + k] for k in range(n)]
+        if once:
+            batched(fleet)
+            loop(twins)
+            for e in fleet + twins:
+                load(e)
+            continue
+        out, ts = {}, {}
+        for name, fn, engines in (("batched", batched, fleet), ("loop", loop, twins)):
+            ts[name] = []
+            for rep in range(reps + 1):                           # (the first pass warms up and is not counted)
+                for e in engines:
+                    load(e)
+                t0 = time.perf_counter()
+                out[name] = fn(engines)
+                if rep:
+                    ts[name].append(1e3 * (time.perf_counter() - t0))
+        assert out["batched"] == out["loop"] and len(set(out["loop"][0])) == 1 and out["loop"][0][0] is not None, (label, n)
+        for a, b in zip(fleet, twins):                              # the same trees, whichever way
+            assert a.size == b.size and np.array_equal(a.states(N, a.size - N), b.states(N, b.size - N))
+        med = {k: float(np.median(v)) for k, v in ts.items()}
+        rows.append(dict(case=label, engines=n, nodes=N, waypoints=len(way), candidates=N * (len(way) + 1), winner=out["loop"][0][0],
+                         appended=len(out["loop"][1][0]),
+                         batched_ms=round(med["batched"], 3), batched_ms_min=round(min(ts["batched"]), 3),
+                         batched_ms_max=round(max(ts["batched"]), 3), loop_ms=round(med["loop"], 3),
+                         loop_ms_min=round(min(ts["loop"]), 3), loop_ms_max=round(max(ts["loop"]), 3),
+                         batched_ms_per_tree=round(med["batched"] / n, 4), loop_ms_per_tree=round(med["loop"] / n, 4),
+                         loop_over_batched=round(med["loop"] / med["batched"], 2)))
+        print("fleet: " + json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    for e in pool.values():
+        e.close()
+    return rows
+
+
 def run_native(max_nodes, reps, once):
     s = lqrrt_amd.systems.BoatAdvanced(0)
     cons = lqrrt_amd.Constraints(s.nstates, s.ncontrols, s.goal_buffer, s.is_feasible)
@@ -262,10 +331,12 @@ def main():
     ap.add_argument("--nodes", type=int, default=100000, help="size of the natively grown tree (0: leave it out)")
     ap.add_argument("--once", action="store_true", help="one untimed search per case, no reference (for a kernel trace)")
     ap.add_argument("--fleet", default=None, help="engines per call, e.g. 4,16,64: time the batched calls against the loop of solo calls instead")
-    ap.add_argument("--via", action="store_true", help="time the search through waypoints (Engine.connect_via_search) instead")
+    ap.add_argument("--via", action="store_true", help="time the search through waypoints (Engine.connect_via_search) instead; with --fleet: the batched pair")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.via:
+    if a.via and a.fleet:
+        rows, name = run_via_fleet([int(v) for v in a.fleet.split(",")], a.reps, a.once), "connect_vias_bench.jsonl"
+    elif a.via:
         rows, name = run_via(a.reps, a.once), "connect_via_bench.jsonl"
     elif a.fleet:
         rows, name = run_fleet([int(v) for v in a.fleet.split(",")], a.reps, a.once), "connect_multi_bench.jsonl"
