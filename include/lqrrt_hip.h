@@ -465,6 +465,32 @@ int lqrrt_connect_search(lqrrt_engine* e, const int32_t* nodes_host, int count, 
 int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, int32_t* ids_out, int cap_ids,
                          void* stream);
 
+/* One tree asked about many goals (Planner.goal_costs / Planner.retarget; not in the reference): lqrrt_connect_search's question for
+ * T targets in one launch.  A tree rooted at the vehicle is a single-source reachability structure; which goal it was grown for
+ * matters to the goal bias of its samples only.  Target t is a goal state goals[t][n] with the box lo[t][d] < x[d] < hi[t][d]
+ * (host arrays [T][n] of doubles, n the model's state count).  The rule is lqrrt_connect_search's with the target's goal and box in
+ * place of the engine's own, for every target independently: the winner of target t is the valid candidate of smallest (cost, node
+ * id) with cost < incumbents[t] -> cost_out[t], node_out[t]; none (or count = 0): cost_out[t] = incumbents[t], node_out[t] = -1.
+ * incumbents = NULL: 2^31-1 for every target.  The engine's own goal and box are neither read nor written.
+ *
+ * Every argument is checked before anything is written or launched, with the rules of lqrrt_connect_search (candidates, id list,
+ * goal_tries, horizon_iters, every incumbent in [1, 2^31-1]) and LQRRT_E_ARG also for T outside [1, 1024], T count workgroups of 64
+ * threads beyond one launch (2^32 - 1 threads), a goal that is not finite, and lo > hi in any dimension.  One launch of T count
+ * workgroups, target-major, every target with a best key of its own; synchronous.  The keys, the target table, the depth table and
+ * the id list go up in one copy into the scratch of lqrrt_connect_search (8 + 288 bytes per target more), which is not part of
+ * lqrrt_engine_footprint; the T keys come back in one copy. */
+int lqrrt_reach_search(lqrrt_engine* e, const double* goals, const double* lo, const double* hi, int T,
+                       const int32_t* nodes_host, int count, int goal_tries, int horizon_iters, const int64_t* incumbents,
+                       int64_t* cost_out, int32_t* node_out, void* stream);
+
+/* lqrrt_reach_commit: lqrrt_connect_commit for one target (goal[n], lo[n], hi[n]) -- replays the chain of candidate `node` toward
+ * that goal and appends its non-empty edges to the tree as a parent chain below it.  ids_out [cap_ids >= goal_tries] receives the
+ * new ids; returns their count.  LQRRT_E_CAPACITY when the tree cannot hold the chain, LQRRT_E_STATE when the chain does not end
+ * in the target's box: the tree is then unchanged.  The engine's own goal and box are not touched, and the loop-time goal
+ * bookkeeping (lqrrt_plan_best) is not rewritten.  Synchronous. */
+int lqrrt_reach_commit(lqrrt_engine* e, const double* goal, const double* lo, const double* hi, int node, int goal_tries,
+                       int horizon_iters, int32_t* ids_out, int cap_ids, void* stream);
+
 /* Tree-wide goal chains through waypoints (Planner.connect_via; not in the reference): lqrrt_connect_search's question with a
  * caller's list of states between the tree and the goal -- the rest of an older plan that the tree no longer holds, the path of a
  * coarser planner.  waypoints_host [Q][n] doubles, Q >= 0 (NULL allowed when Q = 0); a waypoint need be neither a tree node nor a

@@ -121,6 +121,8 @@ SIGNATURES = {
     "lqrrt_refine_commit_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_connect_search": (_I, [_P, _P, _I, _I, _I, _I64, C.POINTER(_I64), C.POINTER(C.c_int32), _P]),
     "lqrrt_connect_commit": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "lqrrt_reach_search": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "lqrrt_reach_commit": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "lqrrt_connect_via_search": (_I, [_P, _P, _I, _P, _I, _I, _I, _I64, C.POINTER(_I64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "lqrrt_connect_via_commit": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
     "lqrrt_connect_search_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -102,11 +102,16 @@ __device__ __forceinline__ int refine_edge(const Params& P, const Geo& g, const 
 }
 
 template <class S>
-__device__ __forceinline__ bool refine_in_goal(const Res& r, const double* x) {   // planner.py:442-447
+__device__ __forceinline__ bool refine_in_goal(const double* lo, const double* hi, const double* x) {   // planner.py:442-447
     bool in = true;
 #pragma unroll
-    for (int d = 0; d < S::N; ++d) in = in && (r.goal_lo[d] < x[d]) && (x[d] < r.goal_hi[d]);
+    for (int d = 0; d < S::N; ++d) in = in && (lo[d] < x[d]) && (x[d] < hi[d]);
     return in;
+}
+
+template <class S>
+__device__ __forceinline__ bool refine_in_goal(const Res& r, const double* x) {   // (the engine's own goal box)
+    return refine_in_goal<S>(r.goal_lo, r.goal_hi, x);
 }
 
 // target t of a chain: plan node t (t < P - 1) or the goal

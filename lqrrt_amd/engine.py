@@ -112,18 +112,28 @@ class Engine(object):
             r.goal_lo[i], r.goal_hi[i] = -np.inf, np.inf
         r.has_goal = 0
         if goal is not None:
-            g = np.asarray(goal, dtype=np.float64)
-            b = np.asarray(goal_buffer, dtype=np.float64)
+            g, lo, hi = self._goal_box(goal, goal_buffer)
             r.has_goal = 1
             for i in range(self.n):
                 r.goal[i] = g[i]
-                r.goal_lo[i] = g[i] - b[i]        # planner.py:482-484
-                r.goal_hi[i] = g[i] + b[i]
+                r.goal_lo[i] = lo[i]
+                r.goal_hi[i] = hi[i]
         nat.check(nat.lib().lqrrt_engine_set_resolution(self.h, C.byref(r)))
         if self.horizon_iters is not None and int(horizon_iters) != self.horizon_iters:
             self.generation += 1      # the edge pools were re-laid out and the tree emptied: bound Tree views are dead
         self.horizon_iters = int(horizon_iters)
         self.epoch += 1
+
+    def _goal_box(self, goal, goal_buffer):
+        """(goal, lo, hi) of a goal state and its buffer, one Python float per state: the ONE statement of the goal box, for the
+        engine's own goal (set_resolution) and for the targets of reach_search / reach_commit."""
+        g = np.asarray(goal, dtype=np.float64)
+        b = np.asarray(goal_buffer, dtype=np.float64)
+        lo, hi = [], []
+        for i in range(self.n):
+            lo.append(g[i] - b[i])                # planner.py:482-484
+            hi.append(g[i] + b[i])
+        return [g[i] for i in range(self.n)], lo, hi
 
     def horizon_iters_state(self):
         return nat.check(nat.lib().lqrrt_engine_horizon_iters(self.h))
@@ -537,6 +547,53 @@ class Engine(object):
         out = np.empty(max(int(goal_tries), 1), dtype=np.int32)
         k = nat.check(nat.lib().lqrrt_connect_commit(self.h, int(node), int(goal_tries), int(horizon_iters), nat.ptr(out), len(out),
                                                      self._stream()))
+        return out[:k].tolist()
+
+    # -- one tree asked about many goals (csrc/engine_reach.hpp; the rule: tests/reach_reference.py) ---------
+    def _targets(self, goals, buffers):
+        """The target table of a reach call: goals [T][n] and their boxes lo / hi [T][n] (`buffers`: one for all, or one per
+        goal), each box what set_resolution computes for the engine's own goal."""
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.ndim != 2 or goals.shape[1] != self.n:
+            raise ValueError("expected goals of shape (T, %d)" % self.n)
+        T = len(goals)
+        try:
+            buffers = np.broadcast_to(np.asarray(buffers, dtype=np.float64), (T, self.n))
+        except ValueError:
+            raise ValueError("expected one goal buffer of %d entries, or one per goal" % self.n)
+        lo, hi = np.empty((T, self.n)), np.empty((T, self.n))
+        for t in range(T):
+            _, lo[t], hi[t] = self._goal_box(goals[t], buffers[t])
+        return goals, lo, hi
+
+    def reach_search(self, goals, buffers, horizon_iters, incumbents=None, goal_tries=8, nodes=None):
+        """connect_search for T targets in one launch (lqrrt_reach_search): target t is the goal state goals[t] with the box
+        goals[t] -/+ buffers[t] (`buffers`: one for all, or one per goal).  Returns [(cost, node) or None] * T, entry t what
+        connect_search returns on an engine whose goal and goal buffer are target t's, with incumbents[t] (None: nothing to
+        beat).  The engine's own goal is not involved, and nothing of the engine changes."""
+        goals, lo, hi = self._targets(goals, buffers)
+        T = len(goals)
+        ids = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        inc = None
+        if incumbents is not None:
+            inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
+            if inc.shape != (T,):
+                raise ValueError("expected one incumbent per goal")
+        cost, node = np.empty(max(T, 1), dtype=np.int64), np.empty(max(T, 1), dtype=np.int32)
+        nat.check(nat.lib().lqrrt_reach_search(self.h, nat.ptr(goals), nat.ptr(lo), nat.ptr(hi), T,
+                                               None if ids is None else nat.ptr(ids), 0 if ids is None else len(ids), int(goal_tries),
+                                               int(horizon_iters), None if inc is None else nat.ptr(inc), nat.ptr(cost), nat.ptr(node),
+                                               self._stream()))
+        return [None if node[t] < 0 else (int(cost[t]), int(node[t])) for t in range(T)]
+
+    def reach_commit(self, goal, buffer, node, horizon_iters, goal_tries=8):
+        """connect_commit toward the target `goal` with the box goal -/+ buffer (lqrrt_reach_commit): appends the chain of
+        candidate `node` below it and returns the new node ids.  NativeError with code E_CAPACITY when the tree cannot hold it,
+        E_STATE when the chain does not reach the target (the tree is then unchanged).  The engine's own goal is not touched."""
+        goals, lo, hi = self._targets(np.asarray(goal, dtype=np.float64).reshape(1, -1), buffer)
+        out = np.empty(max(int(goal_tries), 1), dtype=np.int32)
+        k = nat.check(nat.lib().lqrrt_reach_commit(self.h, nat.ptr(goals), nat.ptr(lo), nat.ptr(hi), int(node), int(goal_tries),
+                                                   int(horizon_iters), nat.ptr(out), len(out), self._stream()))
         return out[:k].tolist()
 
     # -- goal chains through waypoints (csrc/engine_connect_via.hpp; the rule: tests/connect_via_reference.py) ---------

@@ -254,16 +254,20 @@ class Planner:
             #  update_plan's own path ends with sync_numpy_global, which leaves nothing to replay)
             st = np.random.RandomState(seed).get_state()
             eng.set_mt19937(st[1], st[2])
+        self._engine_resolution(eng)
+        run.x0, run.seed = x0, seed
+        if not run.user_sampler:
+            run.sampler = (space, bias, tries_limit)
+        return run
+
+    def _engine_resolution(self, eng):
+        """The planner's resolution, goal and goal box onto the engine.  An unchanged horizon keeps the engine's tree."""
         if self.hfactor:
             # adaptive horizon: rollouts may run hspan[1] steps (include/lqrrt_hip.h, lqrrt_resolution.adaptive)
             eng.set_resolution(self.dt, self.FPR, int(self.hspan[1]), self.error_tol, self.goal, self.constraints.goal_buffer,
                                adaptive=True, hspan_min=int(self.hspan[0]), horizon_iters_state=int(self.horizon_iters))
         else:
             eng.set_resolution(self.dt, self.FPR, self.horizon_iters, self.error_tol, self.goal, self.constraints.goal_buffer)
-        run.x0, run.seed = x0, seed
-        if not run.user_sampler:
-            run.sampler = (space, bias, tries_limit)
-        return run
 
     def _plan_start(self, run, retained):
         """Last step of _plan_begin, after the engine's tree was reset (retained = None) or retained (its stats): sampler, the new
@@ -712,6 +716,87 @@ class Planner:
             table = np.array(seq)
             setattr(self, name, scipy.interpolate.interp1d(self.t_seq, table, axis=0, assume_sorted=True,
                                                            bounds_error=False, fill_value=table[-1].copy()))
+
+    # ------------------------------------------------------------------------------------------ one tree, many goals
+    def goal_costs(self, goals, goal_buffers=None, goal_tries=8, nodes=None):
+        """
+        What would it cost to go to each of these places instead?  Not in the reference.  The tree of the last plan is rooted at
+        the vehicle: which goal it was grown for matters to the goal bias of its samples only.  `goals` is an array [T][nstates];
+        `goal_buffers` is None (constraints.goal_buffer for every goal), one buffer, or one per goal.  For every goal on its own,
+        connect_goal's question is asked of the whole tree (or of the nodes of the id list `nodes`): from a node's state and gain,
+        steer toward the goal up to `goal_tries` times, one _steer(force_arrive=False) edge per try with the fixed horizon
+        `horizon_iters`, until an edge ends inside goal -/+ buffer; the chain with the fewest steps from the root wins (ties to the
+        smaller node id).  All T searches are ONE kernel launch on the device (csrc/reach.hpp); tests/reach_reference.py restates
+        the rule.
+
+        Returns (steps, nodes), two integer arrays of length T: steps[t] is the step count of the cheapest chain to goal t from the
+        root (steps * dt is seconds; -1: no chain reaches it), nodes[t] the tree node that chain leaves from (-1: none).  Reads
+        only: tree, plan, planner.goal and the device footprint stay as they are, and the answer depends neither on what
+        planner.goal currently is nor on whether the plan reached it.  Returns None when there is no tree of this planner on the
+        device (refine_plan's condition).  retarget(goals[t]) then makes goal t the planner's.
+        """
+        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
+            raise NotImplementedError("goal_costs: in callback mode the steer is the user's Python function, which every candidate "
+                                      "of the search would have to run; the device cannot call it.")
+        if int(goal_tries) < 1:
+            raise ValueError("goal_tries must be >= 1.")
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.ndim != 2 or goals.shape[1] != self.nstates or len(goals) < 1:
+            raise ValueError("Expected goals of shape (T, %d) with T >= 1." % self.nstates)
+        buffers = np.asarray(self.constraints.goal_buffer if goal_buffers is None else goal_buffers, dtype=np.float64)
+        if buffers.shape not in [(self.nstates,), (len(goals), self.nstates)]:
+            raise ValueError("Expected goal_buffers to be None, one buffer of %d entries, or one per goal." % self.nstates)
+        if not np.all(buffers >= 0):
+            raise ValueError("A goal buffer must not be negative.")
+        run = self._refine_begin(need_goal=False)
+        if run is None:
+            return None
+        wins = self._engine.reach_search(goals, buffers, run.H, None, goal_tries, nodes)
+        steps = np.array([-1 if w is None else w[0] for w in wins], dtype=np.int64)
+        start = np.array([-1 if w is None else w[1] for w in wins], dtype=np.int64)
+        return steps, start
+
+    def retarget(self, goal, goal_tries=8, nodes=None, finish_on_goal=None):
+        """
+        The goal has moved: a plan to the new one from the tree the planner already holds, without sampling.  Not in the
+        reference, where a new goal means a new plan from one node.  goal_costs' search for the one goal `goal` with
+        constraints.goal_buffer; the winner's edges are appended to the tree below its node, `goal` becomes the planner's goal (as
+        set_goal does) and the engine's, the plan becomes climb(node) + the new nodes and plan_reached_goal is set.  Afterwards
+        connect_goal, connect_via, refine_plan and replan work against the new goal.  `finish_on_goal` is connect_goal's.
+
+        Returns True when the plan was replaced; False, with everything unchanged (planner.goal included), when there is no tree of
+        this planner on the device, no chain reaches the goal, or the tree cannot hold the winner's chain.  With the goal the tree
+        was grown for -- when it still is the planner's -- this is connect_goal, which replaces a plan only with a shorter one.
+        """
+        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
+            raise NotImplementedError("retarget: in callback mode the steer is the user's Python function, which every candidate "
+                                      "of the search would have to run; the device cannot call it.")
+        if int(goal_tries) < 1:
+            raise ValueError("goal_tries must be >= 1.")
+        goal = np.array(goal, dtype=np.float64)
+        if goal.shape != (self.nstates,):
+            raise ValueError("The goal state must have same dimensionality as state space.")
+        run = self._refine_begin(need_goal=False)
+        if run is None:
+            return False
+        if self.goal is not None and np.array_equal(goal, self._grown_goal) and np.array_equal(self.goal, self._grown_goal):
+            return self.connect_goal(goal_tries, nodes, finish_on_goal)
+        eng, buff = self._engine, self.constraints.goal_buffer
+        win = eng.reach_search(goal[None, :], buff, run.H, None, goal_tries, nodes)[0]
+        if win is None:
+            return False
+        cost, node = win
+        try:
+            ids = eng.reach_commit(goal, buff, node, run.H, goal_tries)
+        except nat.NativeError as ex:
+            if ex.code == nat.E_CAPACITY:
+                return False
+            raise
+        self.set_goal(goal)
+        self._engine_resolution(eng)                                # (the horizon is the tree's: the tree stays)
+        self._grown_goal = np.array(self.goal, dtype=np.float64)
+        self._connect_accept(run, cost, node, ids, finish_on_goal)
+        return True
 
     # ------------------------------------------------------------------------------------------ setters
     def set_goal(self, goal):
