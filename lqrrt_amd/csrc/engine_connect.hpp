@@ -64,48 +64,108 @@ static long long connect_depth_of(const lqrrt_engine* e, int node) {
     return depth;
 }
 
+// A search's candidates: the nodes `ids` (null: every node of the tree, and *count becomes its size) of *count entries, each a
+// node of the tree.  One 64-thread workgroup per candidate, `per` candidates per node: they must fit one launch (fewer than 2^32
+// threads), else too_many(count) words the refusal.  k: the engine's index for the messages (< 0: a one-engine call).
+template <class TooMany>
+static int candidates_check(lqrrt_engine* e, const int32_t* ids, int* count, long long per, int k, TooMany too_many) {
+    if (!ids) *count = e->N;
+    if (*count < 0) return fail(LQRRT_E_ARG, "negative candidate count%s", engine_suffix(k).c_str());
+    if (*count * per > 0xffffffffLL / 64) return too_many(*count);
+    for (int c = 0; ids && c < *count; ++c) TRY(range_ok(e, ids[c], 1));
+    return 0;
+}
+
+static int connect_candidates_check(lqrrt_engine* e, const int32_t* ids, int* count, int k) {
+    return candidates_check(e, ids, count, 1, k, [&](int c) {
+        return fail(LQRRT_E_ARG, "%d candidates exceed one launch%s", c, engine_suffix(k).c_str());
+    });
+}
+
+static void connect_fill_args(const lqrrt_engine* e, const int* depth_dev, const int* ids_dev, int count, int tries, int horizon,
+                              ConnectArgs* a) {
+    a->depth = depth_dev;
+    a->nodes = ids_dev;
+    a->count = count; a->tries = tries; a->H = horizon; a->pad = 0;
+    goal_fill(e, e->goal, a->goal);
+}
+
 extern "C" int lqrrt_connect_search(lqrrt_engine* e, const int32_t* nodes_host, int count, int goal_tries, int horizon_iters,
                                     int64_t incumbent, int64_t* cost, int32_t* node_out, void* stream) {
     NOT_GENERIC(e);
     if (!e || !cost || !node_out) return fail(LQRRT_E_ARG, "null argument");
-    if (incumbent < 1 || incumbent > 0x7fffffffLL) return fail(LQRRT_E_ARG, "incumbent cost %lld out of range", (long long)incumbent);
+    TRY(incumbent_check(incumbent, -1));
     TRY(connect_check(e, goal_tries, horizon_iters));
+    TRY(connect_candidates_check(e, nodes_host, &count, -1));
     const int N = e->N;
-    if (!nodes_host) count = N;
-    if (count < 0) return fail(LQRRT_E_ARG, "negative candidate count");
-    if ((long long)count * 64 > 0xffffffffLL) return fail(LQRRT_E_ARG, "%d candidates exceed one launch", count);
-    if (nodes_host)
-        for (int k = 0; k < count; ++k) TRY(range_ok(e, nodes_host[k], 1));
     // the image of the call: head (the key), depth [N], candidate ids [count]
     std::vector<int> img((size_t)8 + N + (nodes_host ? count : 0), 0);
     int* depth = img.data() + 8;
     TRY(connect_depths(e, goal_tries, horizon_iters, depth));
     if (nodes_host && count) memcpy(depth + N, nodes_host, sizeof(int) * (size_t)count);
-    const unsigned long long init = (unsigned long long)incumbent << 32;   // (incumbent, node 0): every candidate at its cost loses
+    const unsigned long long init = incumbent_key(incumbent);   // (incumbent, node 0)
     memcpy(img.data(), &init, sizeof init);
     *cost = incumbent; *node_out = -1;
     if (count == 0) return 0;
     TRY(use_device(e));
     hipStream_t st = (hipStream_t)stream;
     TRY(connect_scratch(e, img.size() - 8));
+    unsigned long long key = init;
+    StreamDrain drain(st);                                      // (img is the source of a copy, key the target of one)
+    drain.arm();
     HIPCHK(hipMemcpyAsync(e->d_con, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, st));
     ConnectArgs a;
-    a.depth = e->d_con + 8;
-    a.nodes = nodes_host ? e->d_con + 8 + N : nullptr;
-    a.count = count; a.tries = goal_tries; a.H = horizon_iters; a.pad = 0;
-    for (int d = 0; d < MAXN; ++d) a.goal[d] = d < e->n ? e->goal[d] : 0.0;
+    connect_fill_args(e, e->d_con + 8, nodes_host ? e->d_con + 8 + N : nullptr, count, goal_tries, horizon_iters, &a);
     unsigned long long* d_key = (unsigned long long*)e->d_con;
     DISPATCH(e, hipLaunchKernelGGL((k_connect_search<S>), dim3((unsigned)count), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P,
                                    e->geo, e->res, e->tv, a, d_key));
     HIPCHK(hipGetLastError());
-    unsigned long long key = init;
     HIPCHK(hipMemcpyAsync(&key, d_key, sizeof key, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                           // (img is the source of a copy until here)
+    HIPCHK(hipStreamSynchronize(st));
+    drain.disarm();
     if (key != init) {
         *cost = (int64_t)(key >> 32);
         *node_out = (int32_t)(key & 0xffffffffull);
     }
     return 0;
+}
+
+// A commit's winner `node` (a node of the tree) with a chain of up to `targets` edges below it: ids_out has room for their ids, and
+// the chain's end stays within 32-bit step counts.  *depth: the steps from the root to `node`.
+static int connect_winner_check(const lqrrt_engine* e, int node, long long targets, int horizon, const int32_t* ids_out, int cap_ids, int k,
+                                long long* depth) {
+    if (!ids_out || cap_ids < targets) return fail(LQRRT_E_ARG, "ids_out must hold %lld ids%s", targets, engine_suffix(k).c_str());
+    *depth = connect_depth_of(e, node);
+    if (*depth + targets * horizon > 0x7fffffffLL)
+        return fail(LQRRT_E_ARG, "tree too deep for 32-bit step counts%s", engine_suffix(k).c_str());
+    return 0;
+}
+
+// The replay of a search's winner, behind the caller's checks: k_refine_commit on the one-node "plan" [node] with the cost prefix
+// [depth], i = j = 0, steers goal_tries times at `goal` and appends the non-empty edges below `node`; the chain ends inside the
+// goal box of `res`.  lqrrt_connect_commit passes the engine's own goal and resolution block, lqrrt_reach_commit a target's
+// (`end`: what the messages call it).
+static int connect_commit_run(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, const double* goal, const Res& res,
+                              const char* end, int32_t* ids_out, int cap_ids, void* stream) {
+    long long depth = 0;
+    TRY(connect_winner_check(e, node, goal_tries, horizon_iters, ids_out, cap_ids, -1, &depth));
+    TRY(use_device(e));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(connect_scratch(e, 2));
+    const int img[10] = {0, 0, 0, 0, 0, 0, 0, 0, node, (int)depth};
+    StreamDrain drain(st);                                      // (img is the source of a copy)
+    drain.arm();
+    HIPCHK(hipMemcpyAsync(e->d_con, img, sizeof img, hipMemcpyHostToDevice, st));
+    RefineArgs a;
+    refine_fill_args(e, e->d_con + 8, 1, goal_tries, horizon_iters, &a);
+    goal_fill(e, goal, a.goal);
+    const int base = e->N;
+    int* d_out = e->d_con + 2;
+    DISPATCH(e, hipLaunchKernelGGL((k_refine_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, res,
+                                   e->tv, a, 0, 0, base, e->fix, d_out));
+    HIPCHK(hipGetLastError());
+    return commit_finish(e, d_out, base, node, ids_out, st, drain, strf("the chain to the %s", end).c_str(),
+                         strf("the chain below node %d does not reach the %s: nothing appended", node, end).c_str());
 }
 
 extern "C" int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, int32_t* ids_out, int cap_ids,
@@ -114,89 +174,39 @@ extern "C" int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, i
     if (!e) return fail(LQRRT_E_ARG, "null engine");
     TRY(connect_check(e, goal_tries, horizon_iters));
     TRY(range_ok(e, node, 1));
-    if (!ids_out || cap_ids < goal_tries) return fail(LQRRT_E_ARG, "ids_out must hold %d ids", goal_tries);
-    const long long depth = connect_depth_of(e, node);
-    if (depth + (long long)goal_tries * horizon_iters > 0x7fffffffLL) return fail(LQRRT_E_ARG, "tree too deep for 32-bit step counts");
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    // the winner's replay is k_refine_commit on the one-node "plan" [node] with the cost prefix [depth]: i = j = 0 steers goal_tries
-    // times at the goal and appends the non-empty edges below `node`
-    TRY(connect_scratch(e, 2));
-    const int img[10] = {0, 0, 0, 0, 0, 0, 0, 0, node, (int)depth};
-    HIPCHK(hipMemcpyAsync(e->d_con, img, sizeof img, hipMemcpyHostToDevice, st));
-    RefineArgs a;
-    refine_fill_args(e, e->d_con + 8, 1, goal_tries, horizon_iters, &a);
-    const int base = e->N;
-    int* d_out = e->d_con + 2;
-    DISPATCH(e, hipLaunchKernelGGL((k_refine_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, e->res,
-                                   e->tv, a, 0, 0, base, e->fix, d_out));
-    HIPCHK(hipGetLastError());
-    int out[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (out[0] < 0) return fail(LQRRT_E_CAPACITY, "tree capacity %d cannot hold the chain to the goal", e->cap);
-    if (!out[2]) return fail(LQRRT_E_STATE, "the chain below node %d does not reach the goal: nothing appended", node);
-    const int count = out[0];
-    std::vector<int> lens((size_t)count);
-    HIPCHK(hipMemcpy(lens.data(), e->tv.elen + base, sizeof(int) * count, hipMemcpyDeviceToHost));
-    refine_adopt(e, node, count, lens.data(), ids_out);
-    return count;
+    return connect_commit_run(e, node, goal_tries, horizon_iters, e->goal, e->res, "goal", ids_out, cap_ids, stream);
 }
 
 // --------------------------------------------------------------------------------------------
-// Several trees per call: lqrrt_connect_search_multi / lqrrt_connect_commit_multi (connect_goals), in the structure of
-// engine_refine.hpp's multi path.  Every argument of every engine is checked before anything is written or launched.  A search call
-// is cut into CHUNKS of up to MULTI_MAX engines with candidates (fewer than 2^32 threads per launch); per chunk one image in device
-// memory -- the keys, then a ConnectDesc per engine, then every engine's depth table and id list -- staged on the host, uploaded
-// in one copy; one launch (connect.hpp k_connect_search_multi); the keys back in one copy.  The chunks of a call are enqueued one
-// after another and waited for once.  The image lives in the scratch of the chunk's first engine that refine_plans' calls use too
-// (refine_multi_scratch, d_refm: not part of the footprint); the calls are synchronous, so nothing reads it after they return.
-// The commit IS refine_commit_multi_run: per winner the one-node plan [v] with the cost prefix [depth[v]], i = j = 0.
-struct ConnectChunk {
-    int first = 0;                        // the engine (index into the call) whose scratch holds the image
-    std::vector<int> members;             // indices (into the call) of the engines that take part in the launch
-    std::vector<char> img;                // host image of the scratch
-};
+// Several trees per call: lqrrt_connect_search_multi / lqrrt_connect_commit_multi (connect_goals), on engine_refine.hpp's multi
+// path: its engine-list check, chunks, scratch (d_refm: not part of the footprint), prototypes, keys and guard.  A search's image per
+// chunk: the keys, then a ConnectDesc per engine, then every engine's depth table and id list; one launch (connect.hpp
+// k_connect_search_multi).  The commit IS refine_commit_multi_run: per winner the one-node plan [v] with the cost prefix
+// [depth[v]], i = j = 0.
 
 // what the two calls check alike, for every engine
 static int connect_multi_check(lqrrt_engine** engines, int n, const int32_t* tries, const int32_t* horizons) {
-    if (!engines || n < 1) return fail(LQRRT_E_ARG, "no engines");
-    if (!tries || !horizons) return fail(LQRRT_E_ARG, "null argument");
-    if (n > 4 * MULTI_MAX) return fail(LQRRT_E_ARG, "at most %d engines per call", 4 * (int)MULTI_MAX);
-    lqrrt_engine* e0 = engines[0];
-    for (int k = 0; k < n; ++k) {
-        lqrrt_engine* e = engines[k];
-        if (!e) return fail(LQRRT_E_ARG, "null engine");
-        NOT_GENERIC(e);
-        for (int q = 0; q < k; ++q)
-            if (engines[q] == e) return fail(LQRRT_E_ARG, "engine %d appears twice", k);
-        if (e->device != e0->device || e->model != e0->model) return fail(LQRRT_E_ARG, "engines of one call share the device and the model");
-        TRY(connect_check(e, tries[k], horizons[k]));
-    }
+    return multi_engines_check(engines, n, tries && horizons, [&](int k) { return connect_check(engines[k], tries[k], horizons[k]); });
+}
+
+// engine k's id list in a call for several engines: none (every node of its tree), or `ids` with their count
+static int multi_id_list(const int32_t* const* nodes, const int32_t* counts, int k, const int32_t** ids, int* count) {
+    *ids = nodes ? nodes[k] : nullptr;
+    if (*ids && !counts) return fail(LQRRT_E_ARG, "an id list without its count (engine %d)", k);
+    *count = *ids ? counts[k] : 0;
     return 0;
 }
 
 static int connect_search_multi_run(lqrrt_engine** engines, int n, const int32_t* const* nodes, const std::vector<int>& counts,
                                     const std::vector<std::vector<int>>& depths, const int32_t* tries, const int32_t* horizons,
-                                    const int64_t* incumbents, int64_t* cost, int32_t* node_out, hipStream_t st,
-                                    std::vector<ConnectChunk>& chunks) {
-    // chunks: up to MULTI_MAX engines with candidates, one 64-thread workgroup per candidate and fewer than 2^32 threads per launch
-    long long cands = 0;
-    for (int k = 0; k < n; ++k) {
-        if (counts[k] == 0) continue;                           // (an empty id list: no launch, no winner)
-        if (chunks.empty() || (int)chunks.back().members.size() == MULTI_MAX || (cands + counts[k]) * 64 > 0xffffffffLL) {
-            chunks.emplace_back();
-            chunks.back().first = k;
-            cands = 0;
-        }
-        chunks.back().members.push_back(k);
-        cands += counts[k];
-    }
-    for (ConnectChunk& c : chunks) {
+                                    const int64_t* incumbents, int64_t* cost, int32_t* node_out, hipStream_t st) {
+    const std::vector<long long> cands(counts.begin(), counts.end());   // (an empty id list: no launch, no winner)
+    std::vector<MultiChunk> chunks = multi_chunks(cands);
+    StreamDrain drain(st);
+    for (MultiChunk& c : chunks) {
         const int m = (int)c.members.size();
-        size_t off = 0;
-        auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 15) / 16 * 16; return at; };
-        const size_t o_keys = carve(sizeof(unsigned long long) * m);
+        Carve carve;
+        carve(sizeof(unsigned long long) * m);                  // the keys
         const size_t o_desc = carve(sizeof(ConnectDesc) * m);
         std::vector<size_t> o_depth((size_t)m), o_ids((size_t)m);
         for (int q = 0; q < m; ++q) {
@@ -204,50 +214,38 @@ static int connect_search_multi_run(lqrrt_engine** engines, int n, const int32_t
             o_depth[q] = carve(sizeof(int) * depths[k].size());
             o_ids[q] = carve(nodes && nodes[k] ? sizeof(int) * (size_t)counts[k] : 0);
         }
-        c.img.assign(off, 0);
+        c.img.assign(carve.off, 0);
         char* d_img = nullptr;
-        TRY(refine_multi_scratch(engines[c.first], off, &d_img));
-        unsigned long long* keys = (unsigned long long*)(c.img.data() + o_keys);
+        TRY(refine_multi_scratch(engines[c.first], carve.off, &d_img));
         ConnectDesc* hd = (ConnectDesc*)(c.img.data() + o_desc);
-        ProtoTable pt;
-        memset(&pt, 0, sizeof pt);
-        size_t lds = 0;
-        std::vector<long long> grid_counts((size_t)m);
         for (int q = 0; q < m; ++q) {
             const int k = c.members[q];
-            lqrrt_engine* e = engines[k];
             const bool listed = nodes && nodes[k];
-            keys[q] = (unsigned long long)incumbents[k] << 32;  // (incumbent, node 0): every candidate at its cost loses
+            ((unsigned long long*)c.img.data())[q] = incumbent_key(incumbents[k]);   // (incumbent, node 0)
             memcpy(c.img.data() + o_depth[q], depths[k].data(), sizeof(int) * depths[k].size());
             if (listed) memcpy(c.img.data() + o_ids[q], nodes[k], sizeof(int) * (size_t)counts[k]);
-            ConnectArgs& a = hd[q].a;
-            a.depth = (const int*)(d_img + o_depth[q]);
-            a.nodes = listed ? (const int*)(d_img + o_ids[q]) : nullptr;
-            a.count = counts[k]; a.tries = tries[k]; a.H = horizons[k]; a.pad = 0;
-            for (int d = 0; d < MAXN; ++d) a.goal[d] = d < e->n ? e->goal[d] : 0.0;
-            hd[q].best = (unsigned long long*)(d_img + o_keys) + q;
-            TRY(multi_sync_proto(e, st));
-            pt.p[q] = e->d_proto;
-            lds = std::max(lds, refine_lds_bytes(e, horizons[k]));
-            grid_counts[q] = counts[k];
+            connect_fill_args(engines[k], (const int*)(d_img + o_depth[q]), listed ? (const int*)(d_img + o_ids[q]) : nullptr, counts[k],
+                              tries[k], horizons[k], &hd[q].a);
+            hd[q].best = (unsigned long long*)d_img + q;
         }
+        ProtoTable pt;
+        size_t lds = 0;
+        TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
         RetainGrid gr;
-        const unsigned grid = retain_grid(grid_counts, gr);
+        const unsigned grid = multi_grid(c, cands, gr);
+        drain.arm();
         HIPCHK(hipMemcpyAsync(d_img, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
         DISPATCH(engines[0], hipLaunchKernelGGL((k_connect_search_multi<S>), dim3(grid), dim3(64), lds, st, pt,
                                                 (const ConnectDesc*)(d_img + o_desc), gr));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c.img.data(), d_img, sizeof(unsigned long long) * m, hipMemcpyDeviceToHost, st));
     }
-    HIPCHK(hipStreamSynchronize(st));
-    for (const ConnectChunk& c : chunks) {
-        const unsigned long long* keys = (const unsigned long long*)c.img.data();
-        for (size_t q = 0; q < c.members.size(); ++q) {
-            const int k = c.members[q];
-            if (keys[q] == (unsigned long long)incumbents[k] << 32) continue;
-            cost[k] = (int64_t)(keys[q] >> 32);
-            node_out[k] = (int32_t)(keys[q] & 0xffffffffull);
-        }
+    std::vector<unsigned long long> keys;
+    TRY(multi_search_keys(chunks, n, incumbents, st, drain, keys));
+    for (int k = 0; k < n; ++k) {
+        if (keys[k] == incumbent_key(incumbents[k])) continue;
+        cost[k] = (int64_t)(keys[k] >> 32);
+        node_out[k] = (int32_t)(keys[k] & 0xffffffffull);
     }
     return 0;
 }
@@ -261,24 +259,17 @@ extern "C" int lqrrt_connect_search_multi(lqrrt_engine** engines, int n, const i
     std::vector<std::vector<int>> depths((size_t)n);
     for (int k = 0; k < n; ++k) {
         lqrrt_engine* e = engines[k];
-        if (incumbents[k] < 1 || incumbents[k] > 0x7fffffffLL)
-            return fail(LQRRT_E_ARG, "incumbent cost %lld out of range (engine %d)", (long long)incumbents[k], k);
-        const bool listed = nodes && nodes[k];
-        if (listed && !counts) return fail(LQRRT_E_ARG, "an id list without its count (engine %d)", k);
-        cnt[k] = listed ? counts[k] : e->N;
-        if (cnt[k] < 0) return fail(LQRRT_E_ARG, "negative candidate count (engine %d)", k);
-        if ((long long)cnt[k] * 64 > 0xffffffffLL) return fail(LQRRT_E_ARG, "%d candidates exceed one launch (engine %d)", cnt[k], k);
-        if (listed)
-            for (int c = 0; c < cnt[k]; ++c) TRY(range_ok(e, nodes[k][c], 1));
+        const int32_t* ids = nullptr;
+        TRY(incumbent_check(incumbents[k], k));
+        TRY(multi_id_list(nodes, counts, k, &ids, &cnt[k]));
+        TRY(connect_candidates_check(e, ids, &cnt[k], k));
         depths[k].assign((size_t)e->N, 0);
         TRY(connect_depths(e, goal_tries[k], horizon_iters[k], depths[k].data()));
     }
     TRY(use_device(engines[0]));
-    hipStream_t st = (hipStream_t)stream;
     for (int k = 0; k < n; ++k) { cost_out[k] = incumbents[k]; node_out[k] = -1; }
-    std::vector<ConnectChunk> chunks;                           // (outlives every copy of the call, also when the call fails)
-    const int rc = connect_search_multi_run(engines, n, nodes, cnt, depths, goal_tries, horizon_iters, incumbents, cost_out, node_out, st, chunks);
-    return rc ? refine_multi_fail(rc, st) : 0;
+    return connect_search_multi_run(engines, n, nodes, cnt, depths, goal_tries, horizon_iters, incumbents, cost_out, node_out,
+                                    (hipStream_t)stream);
 }
 
 extern "C" int lqrrt_connect_commit_multi(lqrrt_engine** engines, int n, const int32_t* nodes, const int32_t* goal_tries,
@@ -292,19 +283,13 @@ extern "C" int lqrrt_connect_commit_multi(lqrrt_engine** engines, int n, const i
     std::vector<int32_t> ones((size_t)n, 1), ij((size_t)n, -1);
     for (int k = 0; k < n; ++k) {
         if (nodes[k] == -1) continue;                           // an engine without a winner
-        lqrrt_engine* e = engines[k];
-        TRY(range_ok(e, nodes[k], 1));
-        if (!ids_out[k] || cap_ids[k] < goal_tries[k]) return fail(LQRRT_E_ARG, "ids_out of engine %d must hold %d ids", k, goal_tries[k]);
-        const long long depth = connect_depth_of(e, nodes[k]);
-        if (depth + (long long)goal_tries[k] * horizon_iters[k] > 0x7fffffffLL)
-            return fail(LQRRT_E_ARG, "tree too deep for 32-bit step counts (engine %d)", k);
+        long long depth = 0;
+        TRY(range_ok(engines[k], nodes[k], 1));
+        TRY(connect_winner_check(engines[k], nodes[k], goal_tries[k], horizon_iters[k], ids_out[k], cap_ids[k], k, &depth));
         bufs[k] = {nodes[k], (int)depth};
         ij[k] = 0;
     }
     TRY(use_device(engines[0]));
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<RefineChunk> chunks;                            // (outlives every copy of the call, also when the call fails)
-    const int rc = refine_commit_multi_run(engines, n, bufs, ones.data(), goal_tries, horizon_iters, ij.data(), ij.data(), ids_out, counts_out,
-                                           st, chunks);
-    return rc ? refine_multi_fail(rc, st) : 0;
+    return refine_commit_multi_run(engines, n, bufs, ones.data(), goal_tries, horizon_iters, ij.data(), ij.data(), ids_out, counts_out,
+                                   (hipStream_t)stream);
 }

@@ -11,6 +11,8 @@
 //
 // One image per call in d_con: the head of 8 ints (the key; a commit's out[3] behind it), the waypoints [Q][n] (8-byte aligned
 // behind the head), the depth table [N], the id list [count].  One copy up, one launch, one read-back.
+//
+// The checks, the argument block and the key's decoding below serve the calls for several trees too (engine_connect_via_multi.hpp).
 // --------------------------------------------------------------------------------------------
 
 // what the two calls check alike, before anything is written; Q waypoints of e->n doubles
@@ -23,11 +25,49 @@ static int connect_via_check(lqrrt_engine* e, const double* way, int Q, int trie
     return 0;
 }
 
-static void connect_via_fill_args(const lqrrt_engine* e, int Q, int tries, int horizon, ConnectViaArgs* a) {
-    a->way = (const double*)(e->d_con + 8);
+// a candidate's position in the key is its place in the id list: the list is strictly ascending, so ties go to the smaller node
+static int ids_ascending_check(const int32_t* ids, int count, int k) {
+    for (int c = 1; ids && c < count; ++c)
+        if (ids[c] <= ids[c - 1])
+            return fail(LQRRT_E_ARG, "the id list is not strictly ascending at position %d%s", c, engine_suffix(k).c_str());
+    return 0;
+}
+
+// a search's candidates: connect's list, Q + 1 candidates per node
+static int connect_via_candidates_check(lqrrt_engine* e, const int32_t* ids, int* count, int Q, int k) {
+    TRY(candidates_check(e, ids, count, (long long)Q + 1, k, [&](int c) {
+        return fail(LQRRT_E_ARG, "%d nodes with %d waypoints: %lld candidates exceed one launch%s", c, Q, (long long)c * ((long long)Q + 1),
+                    engine_suffix(k).c_str());
+    }));
+    return ids_ascending_check(ids, *count, k);
+}
+
+// The 32-bit bound of a search: the deepest CANDIDATE (of the id list, or of the tree) with every one of its Q + tries targets' edges
+// at full length.  It is not connect's and reach's bound, which holds every node of the tree to `tries` edges while the table is
+// filled (connect_depths): a chain here is Q edges longer, and only the nodes it may start from count, so the table is filled with
+// no edges to come (tries = 0) and the bound is taken here, over the candidates.
+static int connect_via_deepest_check(const int* depth, int N, const int32_t* ids, int count, int Q, int tries, int horizon, int k) {
+    long long deepest = 0;
+    for (int c = 0; c < (ids ? count : N); ++c) deepest = std::max(deepest, (long long)depth[ids ? ids[c] : c]);
+    if (count && deepest + ((long long)Q + tries) * horizon > 0x7fffffffLL)
+        return fail(LQRRT_E_ARG, "tree too deep for 32-bit step counts%s", engine_suffix(k).c_str());
+    return 0;
+}
+
+// the argument block of a chain over the waypoints at way_dev; a search adds its depth table and candidates
+static void connect_via_fill_args(const lqrrt_engine* e, const double* way_dev, int Q, int tries, int horizon, ConnectViaArgs* a) {
+    a->way = way_dev;
     a->nodes = nullptr; a->depth = nullptr;
     a->count = 0; a->Q = Q; a->tries = tries; a->H = horizon;
-    for (int d = 0; d < MAXN; ++d) a->goal[d] = d < e->n ? e->goal[d] : 0.0;
+    goal_fill(e, e->goal, a->goal);
+}
+
+// a winner's key: (cost, position in the candidate list * (Q + 1) + j)
+static void connect_via_decode(unsigned long long key, const int32_t* ids, int Q, int64_t* cost, int32_t* node, int32_t* j) {
+    const long long cand = (long long)(key & 0xffffffffull), pos = cand / ((long long)Q + 1);
+    *cost = (int64_t)(key >> 32);
+    *node = ids ? ids[pos] : (int32_t)pos;
+    *j = (int32_t)(cand - pos * ((long long)Q + 1));
 }
 
 extern "C" int lqrrt_connect_via_search(lqrrt_engine* e, const int32_t* nodes_host, int count, const double* waypoints_host, int Q,
@@ -35,42 +75,31 @@ extern "C" int lqrrt_connect_via_search(lqrrt_engine* e, const int32_t* nodes_ho
                                         int32_t* j_out, void* stream) {
     NOT_GENERIC(e);
     if (!e || !cost || !node_out || !j_out) return fail(LQRRT_E_ARG, "null argument");
-    if (incumbent < 1 || incumbent > 0x7fffffffLL) return fail(LQRRT_E_ARG, "incumbent cost %lld out of range", (long long)incumbent);
+    TRY(incumbent_check(incumbent, -1));
     TRY(connect_via_check(e, waypoints_host, Q, goal_tries, horizon_iters));
+    TRY(connect_via_candidates_check(e, nodes_host, &count, Q, -1));
     const int N = e->N;
-    if (!nodes_host) count = N;
-    if (count < 0) return fail(LQRRT_E_ARG, "negative candidate count");
-    if ((long long)count * ((long long)Q + 1) * 64 > 0xffffffffLL)
-        return fail(LQRRT_E_ARG, "%d nodes with %d waypoints: %lld candidates exceed one launch", count, Q, (long long)count * ((long long)Q + 1));
-    if (nodes_host)
-        for (int k = 0; k < count; ++k) {
-            TRY(range_ok(e, nodes_host[k], 1));
-            if (k > 0 && nodes_host[k] <= nodes_host[k - 1]) return fail(LQRRT_E_ARG, "the id list is not strictly ascending at position %d", k);
-        }
     // the image of the call: head (the key), waypoints [Q][n], depth [N], candidate ids [count]
     const size_t way_ints = (size_t)2 * Q * e->n;
     std::vector<int> img((size_t)8 + way_ints + N + (nodes_host ? count : 0), 0);
     int* depth = img.data() + 8 + way_ints;
     TRY(connect_depths(e, 0, horizon_iters, depth));
-    long long deepest = 0;                                      // the deepest candidate, with every target's edge at full length
-    if (nodes_host)
-        for (int k = 0; k < count; ++k) deepest = std::max(deepest, (long long)depth[nodes_host[k]]);
-    else
-        for (int v = 0; v < N; ++v) deepest = std::max(deepest, (long long)depth[v]);
-    if (count && deepest + ((long long)Q + goal_tries) * horizon_iters > 0x7fffffffLL)
-        return fail(LQRRT_E_ARG, "tree too deep for 32-bit step counts");
+    TRY(connect_via_deepest_check(depth, N, nodes_host, count, Q, goal_tries, horizon_iters, -1));
     if (way_ints) memcpy(img.data() + 8, waypoints_host, sizeof(int) * way_ints);
     if (nodes_host && count) memcpy(depth + N, nodes_host, sizeof(int) * (size_t)count);
-    const unsigned long long init = (unsigned long long)incumbent << 32;   // (incumbent, candidate 0): every candidate at its cost loses
+    const unsigned long long init = incumbent_key(incumbent);   // (incumbent, candidate 0)
     memcpy(img.data(), &init, sizeof init);
     *cost = incumbent; *node_out = -1; *j_out = -1;
     if (count == 0) return 0;
     TRY(use_device(e));
     hipStream_t st = (hipStream_t)stream;
     TRY(connect_scratch(e, img.size() - 8));
+    unsigned long long key = init;
+    StreamDrain drain(st);                                      // (img is the source of a copy, key the target of one)
+    drain.arm();
     HIPCHK(hipMemcpyAsync(e->d_con, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, st));
     ConnectViaArgs a;
-    connect_via_fill_args(e, Q, goal_tries, horizon_iters, &a);
+    connect_via_fill_args(e, (const double*)(e->d_con + 8), Q, goal_tries, horizon_iters, &a);
     a.depth = e->d_con + 8 + way_ints;
     a.nodes = nodes_host ? a.depth + N : nullptr;
     a.count = count;
@@ -79,16 +108,20 @@ extern "C" int lqrrt_connect_via_search(lqrrt_engine* e, const int32_t* nodes_ho
     DISPATCH(e, hipLaunchKernelGGL((k_connect_via_search<S>), dim3(grid), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo,
                                    e->res, e->tv, a, d_key));
     HIPCHK(hipGetLastError());
-    unsigned long long key = init;
     HIPCHK(hipMemcpyAsync(&key, d_key, sizeof key, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                           // (img is the source of a copy until here)
-    if (key != init) {
-        const long long c = (long long)(key & 0xffffffffull), pos = c / (Q + 1);
-        *cost = (int64_t)(key >> 32);
-        *node_out = nodes_host ? nodes_host[pos] : (int32_t)pos;
-        *j_out = (int32_t)(c - pos * (Q + 1));
-    }
+    HIPCHK(hipStreamSynchronize(st));
+    drain.disarm();
+    if (key != init) connect_via_decode(key, nodes_host, Q, cost, node_out, j_out);
     return 0;
+}
+
+// a commit's winner (node, j): what connect_winner_check asks of its Q - j + tries targets; *room: their number
+static int connect_via_winner_check(lqrrt_engine* e, int node, int j, int Q, int tries, int horizon, const int32_t* ids_out, int cap_ids,
+                                    int k, long long* depth, int* room) {
+    TRY(range_ok(e, node, 1));
+    if (j < 0 || j > Q) return fail(LQRRT_E_ARG, "first waypoint %d outside [0, %d]%s", j, Q, engine_suffix(k).c_str());
+    *room = (int)((long long)Q - j + tries);
+    return connect_winner_check(e, node, (long long)Q - j + tries, horizon, ids_out, cap_ids, k, depth);
 }
 
 extern "C" int lqrrt_connect_via_commit(lqrrt_engine* e, int node, int j, const double* waypoints_host, int Q, int goal_tries,
@@ -96,34 +129,25 @@ extern "C" int lqrrt_connect_via_commit(lqrrt_engine* e, int node, int j, const 
     NOT_GENERIC(e);
     if (!e) return fail(LQRRT_E_ARG, "null engine");
     TRY(connect_via_check(e, waypoints_host, Q, goal_tries, horizon_iters));
-    TRY(range_ok(e, node, 1));
-    if (j < 0 || j > Q) return fail(LQRRT_E_ARG, "first waypoint %d outside [0, %d]", j, Q);
-    const long long room = (long long)Q - j + goal_tries;
-    if (!ids_out || cap_ids < room) return fail(LQRRT_E_ARG, "ids_out must hold %lld ids", room);
-    const long long depth = connect_depth_of(e, node);
-    if (depth + room * horizon_iters > 0x7fffffffLL) return fail(LQRRT_E_ARG, "tree too deep for 32-bit step counts");
+    long long depth = 0;
+    int room = 0;
+    TRY(connect_via_winner_check(e, node, j, Q, goal_tries, horizon_iters, ids_out, cap_ids, -1, &depth, &room));
     TRY(use_device(e));
     hipStream_t st = (hipStream_t)stream;
     const size_t way_ints = (size_t)2 * Q * e->n;
     TRY(connect_scratch(e, way_ints));
     std::vector<int> img((size_t)8 + way_ints, 0);
     if (way_ints) memcpy(img.data() + 8, waypoints_host, sizeof(int) * way_ints);
+    StreamDrain drain(st);                                      // (img is the source of a copy)
+    drain.arm();
     HIPCHK(hipMemcpyAsync(e->d_con, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, st));
     ConnectViaArgs a;
-    connect_via_fill_args(e, Q, goal_tries, horizon_iters, &a);
+    connect_via_fill_args(e, (const double*)(e->d_con + 8), Q, goal_tries, horizon_iters, &a);
     const int base = e->N;
     int* d_out = e->d_con + 2;
     DISPATCH(e, hipLaunchKernelGGL((k_connect_via_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo,
                                    e->res, e->tv, a, node, j, (int)depth, base, e->fix, d_out));
     HIPCHK(hipGetLastError());
-    int out[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                           // (img is the source of a copy until here)
-    if (out[0] < 0) return fail(LQRRT_E_CAPACITY, "tree capacity %d cannot hold the chain to the goal", e->cap);
-    if (!out[2]) return fail(LQRRT_E_STATE, "the chain of candidate (%d, %d) does not reach the goal: nothing appended", node, j);
-    const int count = out[0];
-    std::vector<int> lens((size_t)count);
-    HIPCHK(hipMemcpy(lens.data(), e->tv.elen + base, sizeof(int) * count, hipMemcpyDeviceToHost));
-    refine_adopt(e, node, count, lens.data(), ids_out);
-    return count;
+    return commit_finish(e, d_out, base, node, ids_out, st, drain, "the chain to the goal",
+                         strf("the chain of candidate (%d, %d) does not reach the goal: nothing appended", node, j).c_str());
 }

@@ -35,13 +35,10 @@ extern "C" int lqrrt_reach_search(lqrrt_engine* e, const double* goals, const do
     if (!e || !goals || !lo || !hi || !cost_out || !node_out) return fail(LQRRT_E_ARG, "null argument");
     if (T < 1 || T > 1024) return fail(LQRRT_E_ARG, "%d targets (1 to 1024 per call)", T);
     TRY(connect_check(e, goal_tries, horizon_iters));
+    TRY(candidates_check(e, nodes_host, &count, T, -1, [&](int c) {
+        return fail(LQRRT_E_ARG, "%d targets of %d candidates: %lld workgroups exceed one launch", T, c, (long long)T * c);
+    }));
     const int N = e->N, n = e->n;
-    if (!nodes_host) count = N;
-    if (count < 0) return fail(LQRRT_E_ARG, "negative candidate count");
-    if ((long long)T * count * 64 > 0xffffffffLL)
-        return fail(LQRRT_E_ARG, "%d targets of %d candidates: %lld workgroups exceed one launch", T, count, (long long)T * count);
-    if (nodes_host)
-        for (int k = 0; k < count; ++k) TRY(range_ok(e, nodes_host[k], 1));
     for (int t = 0; t < T; ++t) {
         const long long inc = incumbents ? (long long)incumbents[t] : 0x7fffffffLL;
         if (inc < 1 || inc > 0x7fffffffLL) return fail(LQRRT_E_ARG, "incumbent cost %lld of target %d out of range", inc, t);
@@ -58,14 +55,17 @@ extern "C" int lqrrt_reach_search(lqrrt_engine* e, const double* goals, const do
     for (int t = 0; t < T; ++t) {
         cost_out[t] = incumbents ? incumbents[t] : 0x7fffffffLL;
         node_out[t] = -1;
-        img[(size_t)t] = (unsigned long long)cost_out[t] << 32;  // (incumbent, node 0): every candidate at its cost loses
+        img[(size_t)t] = incumbent_key(cost_out[t]);             // (incumbent, node 0)
         reach_target_fill(e, goals + (size_t)t * n, lo + (size_t)t * n, hi + (size_t)t * n, tab[t].goal, tab[t].lo, tab[t].hi);
     }
     if (count == 0) return 0;
     TRY(use_device(e));
     hipStream_t st = (hipStream_t)stream;
     TRY(connect_scratch(e, img.size() * 2));                    // (the scratch counts ints behind its head of 8; the image starts at the head)
+    std::vector<unsigned long long> keys((size_t)T);
+    StreamDrain drain(st);                                      // (img is the source of a copy, keys the target of one)
     char* d_img = (char*)e->d_con;
+    drain.arm();
     HIPCHK(hipMemcpyAsync(d_img, base, sizeof(unsigned long long) * img.size(), hipMemcpyHostToDevice, st));
     ReachArgs a;
     a.targets = (const ReachTarget*)(d_img + o_tab);
@@ -77,9 +77,9 @@ extern "C" int lqrrt_reach_search(lqrrt_engine* e, const double* goals, const do
     DISPATCH(e, hipLaunchKernelGGL((k_reach_search<S>), dim3(grid), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, e->res,
                                    e->tv, a, d_keys));
     HIPCHK(hipGetLastError());
-    std::vector<unsigned long long> keys((size_t)T);
     HIPCHK(hipMemcpyAsync(keys.data(), d_keys, sizeof(unsigned long long) * (size_t)T, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                           // (img is the source of a copy until here)
+    HIPCHK(hipStreamSynchronize(st));
+    drain.disarm();
     for (int t = 0; t < T; ++t) {
         if (keys[(size_t)t] == img[(size_t)t]) continue;
         cost_out[t] = (int64_t)(keys[(size_t)t] >> 32);
@@ -88,6 +88,8 @@ extern "C" int lqrrt_reach_search(lqrrt_engine* e, const double* goals, const do
     return 0;
 }
 
+// lqrrt_connect_commit's replay (connect_commit_run) with the target as the chain's goal and a copy of the resolution block whose
+// goal box is the target's
 extern "C" int lqrrt_reach_commit(lqrrt_engine* e, const double* goal, const double* lo, const double* hi, int node, int goal_tries,
                                   int horizon_iters, int32_t* ids_out, int cap_ids, void* stream) {
     NOT_GENERIC(e);
@@ -95,33 +97,8 @@ extern "C" int lqrrt_reach_commit(lqrrt_engine* e, const double* goal, const dou
     TRY(connect_check(e, goal_tries, horizon_iters));
     TRY(range_ok(e, node, 1));
     TRY(reach_target_check(e, goal, lo, hi, 0));
-    if (!ids_out || cap_ids < goal_tries) return fail(LQRRT_E_ARG, "ids_out must hold %d ids", goal_tries);
-    const long long depth = connect_depth_of(e, node);
-    if (depth + (long long)goal_tries * horizon_iters > 0x7fffffffLL) return fail(LQRRT_E_ARG, "tree too deep for 32-bit step counts");
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    // lqrrt_connect_commit's replay -- k_refine_commit on the one-node "plan" [node] with the cost prefix [depth], i = j = 0 -- with
-    // the target as the chain's goal and a copy of the resolution block whose goal box is the target's
-    TRY(connect_scratch(e, 2));
-    const int img[10] = {0, 0, 0, 0, 0, 0, 0, 0, node, (int)depth};
-    HIPCHK(hipMemcpyAsync(e->d_con, img, sizeof img, hipMemcpyHostToDevice, st));
-    RefineArgs a;
-    refine_fill_args(e, e->d_con + 8, 1, goal_tries, horizon_iters, &a);
+    double g[MAXN];
     Res res = e->res;
-    reach_target_fill(e, goal, lo, hi, a.goal, res.goal_lo, res.goal_hi);
-    const int base = e->N;
-    int* d_out = e->d_con + 2;
-    DISPATCH(e, hipLaunchKernelGGL((k_refine_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, res,
-                                   e->tv, a, 0, 0, base, e->fix, d_out));
-    HIPCHK(hipGetLastError());
-    int out[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (out[0] < 0) return fail(LQRRT_E_CAPACITY, "tree capacity %d cannot hold the chain to the target", e->cap);
-    if (!out[2]) return fail(LQRRT_E_STATE, "the chain below node %d does not reach the target: nothing appended", node);
-    const int count = out[0];
-    std::vector<int> lens((size_t)count);
-    HIPCHK(hipMemcpy(lens.data(), e->tv.elen + base, sizeof(int) * count, hipMemcpyDeviceToHost));
-    refine_adopt(e, node, count, lens.data(), ids_out);
-    return count;
+    reach_target_fill(e, goal, lo, hi, g, res.goal_lo, res.goal_hi);
+    return connect_commit_run(e, node, goal_tries, horizon_iters, g, res, "target", ids_out, cap_ids, stream);
 }

@@ -1,6 +1,60 @@
 // ABI: plan refinement -- the shortcut search over a found plan and the commit of its winner (Planner.refine_plan; kernels in
 // refine.hpp, the rule restated from the C oracle's primitives in tests/refine_reference.py).  Fragment of engine.hip.
+//
+// The refinement is the first of a family of calls -- goal connection (engine_connect.hpp), one tree asked about many goals
+// (engine_reach.hpp), goal chains through waypoints (engine_connect_via.hpp, engine_connect_via_multi.hpp) -- that search candidates
+// in one launch and replay the winner in another.  What their host sides share is stated once, here where its first user is: the
+// rules of an argument (incumbent_check, goal_fill), the end of a one-engine commit (commit_finish), the guard of a call's host
+// images (StreamDrain), and for the calls that take several engines the engine-list check, the chunks, their images' layout and
+// what is read back from them (MultiChunk and the multi_* functions).  The kernel launched, its descriptor and the decoding of a
+// key are each caller's own.
 // --------------------------------------------------------------------------------------------
+
+// " (engine k)" behind a message of a call for several engines; nothing behind that of a one-engine call (k < 0)
+static std::string engine_suffix(int k) { return k < 0 ? std::string() : " (engine " + std::to_string(k) + ")"; }
+
+static std::string strf(const char* fmt, ...) {
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
+
+// the step count a search has to beat
+static int incumbent_check(int64_t incumbent, int k) {
+    if (incumbent < 1 || incumbent > 0x7fffffffLL)
+        return fail(LQRRT_E_ARG, "incumbent cost %lld out of range%s", (long long)incumbent, engine_suffix(k).c_str());
+    return 0;
+}
+
+// a search's best key before the launch, (incumbent, 0 ..): every candidate at the incumbent's cost loses against it
+static unsigned long long incumbent_key(int64_t incumbent) { return (unsigned long long)incumbent << 32; }
+
+// `goal` (the model's n entries) as the kernels' argument blocks hold it
+static void goal_fill(const lqrrt_engine* e, const double* goal, double* out) {
+    for (int d = 0; d < MAXN; ++d) out[d] = d < e->n ? goal[d] : 0.0;
+}
+
+// A call stages images in host memory of its own and reads results back into it; the copies are asynchronous and the call waits
+// for them once, at its end.  When it leaves before that -- a later enqueue failed -- a copy may still be in flight, so the stream
+// is drained before the memory goes: declare the guard BEHIND the memory it protects, arm it at the first copy, disarm it after
+// the synchronise that succeeded.  (What a read-back targets after a synchronise that FAILED no second one can protect.)
+struct StreamDrain {
+    hipStream_t st;
+    bool armed = false;
+    explicit StreamDrain(hipStream_t s) : st(s) {}
+    StreamDrain(const StreamDrain&) = delete;
+    void arm() { armed = true; }
+    void disarm() { armed = false; }
+    ~StreamDrain() {
+        if (!armed) return;
+        const std::string keep = g_err;
+        (void)hipStreamSynchronize(st);
+        g_err = keep;
+    }
+};
 
 // Checks a plan (a parent chain from the root) and fills `buf` with its ids and cost prefix [2][P].  Writes nothing else.
 static int refine_check(lqrrt_engine* e, const int32_t* plan, int P, int tries, int horizon, std::vector<int>& buf) {
@@ -24,16 +78,25 @@ static int refine_check(lqrrt_engine* e, const int32_t* plan, int P, int tries, 
     return 0;
 }
 
+// one 64-thread workgroup per candidate (i, j) of a plan: the grid's thread count must stay below 2^32
+static long long refine_candidates(int P) { return (long long)P * (P - 1) / 2; }
+
+static int refine_candidates_check(int P) {
+    if (refine_candidates(P) * 64 > 0xffffffffLL)
+        return fail(LQRRT_E_ARG, "plan of %d nodes: %lld candidates exceed one launch (at most 11586 nodes)", P, refine_candidates(P));
+    return 0;
+}
+
 static void refine_fill_args(const lqrrt_engine* e, const int* plan_dev, int P, int tries, int horizon, RefineArgs* a) {
     a->plan = plan_dev;
     a->prefix = plan_dev + P;
     a->P = P; a->tries = tries; a->H = horizon; a->pad = 0;
-    for (int d = 0; d < MAXN; ++d) a->goal[d] = d < e->n ? e->goal[d] : 0.0;
+    goal_fill(e, e->goal, a->goal);
 }
 
 // Checks a plan and uploads its ids and cost prefix; `buf` holds the host copy until the caller has synchronised the stream.
 static int refine_prepare(lqrrt_engine* e, const int32_t* plan, int P, int tries, int horizon, std::vector<int>& buf, RefineArgs* a,
-                          hipStream_t st) {
+                          hipStream_t st, StreamDrain& drain) {
     TRY(refine_check(e, plan, P, tries, horizon, buf));
     if (P > e->ref_cap) {
         const size_t keep = g_dalloc_bytes;
@@ -45,6 +108,7 @@ static int refine_prepare(lqrrt_engine* e, const int32_t* plan, int P, int tries
         if (rc) return rc;
         e->ref_cap = P;
     }
+    drain.arm();
     HIPCHK(hipMemcpyAsync(e->d_ref, buf.data(), sizeof(int) * buf.size(), hipMemcpyHostToDevice, st));
     refine_fill_args(e, e->d_ref, P, tries, horizon, a);
     return 0;
@@ -58,27 +122,26 @@ extern "C" int lqrrt_refine_search(lqrrt_engine* e, const int32_t* plan_host, in
                                    int64_t incumbent, int64_t* cost, int32_t* i_out, int32_t* j_out, void* stream) {
     NOT_GENERIC(e);
     if (!e || !cost || !i_out || !j_out) return fail(LQRRT_E_ARG, "null argument");
-    if (incumbent < 1 || incumbent > 0x7fffffffLL) return fail(LQRRT_E_ARG, "incumbent cost %lld out of range", (long long)incumbent);
+    TRY(incumbent_check(incumbent, -1));
     TRY(use_device(e));
     hipStream_t st = (hipStream_t)stream;
     std::vector<int> buf;
-    RefineArgs a;
-    TRY(refine_prepare(e, plan_host, P, goal_tries, horizon_iters, buf, &a, st));
-    *cost = incumbent; *i_out = -1; *j_out = -1;
-    const unsigned long long init = (unsigned long long)incumbent << 32;   // (incumbent, 0, 0): every candidate at its cost loses
+    const unsigned long long init = incumbent_key(incumbent);
     unsigned long long key = init;
+    StreamDrain drain(st);                                      // (buf and init are sources of copies, key the target of one)
+    RefineArgs a;
+    TRY(refine_prepare(e, plan_host, P, goal_tries, horizon_iters, buf, &a, st, drain));
+    *cost = incumbent; *i_out = -1; *j_out = -1;
     if (P >= 2) {
-        // one 64-thread workgroup per candidate: the grid's thread count must stay below 2^32
-        if ((long long)P * (P - 1) / 2 * 64 > 0xffffffffLL)
-            return fail(LQRRT_E_ARG, "plan of %d nodes: %lld candidates exceed one launch (at most 11586 nodes)", P, (long long)P * (P - 1) / 2);
+        TRY(refine_candidates_check(P));
         HIPCHK(hipMemcpyAsync(e->d_ref_key, &init, sizeof init, hipMemcpyHostToDevice, st));
-        const unsigned ncand = (unsigned)((long long)P * (P - 1) / 2);
-        DISPATCH(e, hipLaunchKernelGGL((k_refine_search<S>), dim3(ncand), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo,
-                                       e->res, e->tv, a, e->d_ref_key));
+        DISPATCH(e, hipLaunchKernelGGL((k_refine_search<S>), dim3((unsigned)refine_candidates(P)), dim3(64), refine_lds_bytes(e, horizon_iters),
+                                       st, e->P, e->geo, e->res, e->tv, a, e->d_ref_key));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&key, e->d_ref_key, sizeof key, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
+    drain.disarm();
     if (key != init) {
         *cost = (int64_t)(key >> 32);
         *i_out = (int32_t)((key >> 16) & 0xffff);
@@ -106,6 +169,25 @@ static void refine_adopt(lqrrt_engine* e, int parent, int count, const int* lens
     e->tot.tree_size = e->N;
 }
 
+// The end of a one-engine commit, behind the launch of a replay that appends below tree size `base` and writes d_out[3] (the node
+// count or -1: no room, -, 1: the chain reached its goal): the read-back, the call's one synchronise, the refusals, the new
+// edges' lengths and the host mirrors.  `holds`: what the tree cannot hold; `unreached`: the message of a chain that fell short.
+// Returns the number of nodes appended below `parent`, their ids in ids_out.
+static int commit_finish(lqrrt_engine* e, const int* d_out, int base, int parent, int32_t* ids_out, hipStream_t st, StreamDrain& drain,
+                         const char* holds, const char* unreached) {
+    int out[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    drain.disarm();
+    if (out[0] < 0) return fail(LQRRT_E_CAPACITY, "tree capacity %d cannot hold %s", e->cap, holds);
+    if (!out[2]) return fail(LQRRT_E_STATE, "%s", unreached);
+    const int count = out[0];
+    std::vector<int> lens((size_t)count);
+    HIPCHK(hipMemcpy(lens.data(), e->tv.elen + base, sizeof(int) * count, hipMemcpyDeviceToHost));
+    refine_adopt(e, parent, count, lens.data(), ids_out);
+    return count;
+}
+
 extern "C" int lqrrt_refine_commit(lqrrt_engine* e, const int32_t* plan_host, int P, int goal_tries, int horizon_iters, int i, int j,
                                    int32_t* ids_out, int cap_ids, void* stream) {
     NOT_GENERIC(e);
@@ -115,39 +197,61 @@ extern "C" int lqrrt_refine_commit(lqrrt_engine* e, const int32_t* plan_host, in
     TRY(use_device(e));
     hipStream_t st = (hipStream_t)stream;
     std::vector<int> buf;
+    StreamDrain drain(st);                                      // (buf is the source of a copy)
     RefineArgs a;
-    TRY(refine_prepare(e, plan_host, P, goal_tries, horizon_iters, buf, &a, st));
+    TRY(refine_prepare(e, plan_host, P, goal_tries, horizon_iters, buf, &a, st, drain));
     const int base = e->N;
     int* d_out = (int*)(e->d_ref_key + 1);
     DISPATCH(e, hipLaunchKernelGGL((k_refine_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, e->res,
                                    e->tv, a, i, j, base, e->fix, d_out));
     HIPCHK(hipGetLastError());
-    int out[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (out[0] < 0) return fail(LQRRT_E_CAPACITY, "tree capacity %d cannot hold the refined chain", e->cap);
-    if (!out[2]) return fail(LQRRT_E_STATE, "candidate (%d, %d) does not reach the goal: nothing appended", i, j);
-    const int count = out[0];
-    std::vector<int> lens((size_t)count);
-    HIPCHK(hipMemcpy(lens.data(), e->tv.elen + base, sizeof(int) * count, hipMemcpyDeviceToHost));
-    refine_adopt(e, plan_host[i], count, lens.data(), ids_out);
-    return count;
+    return commit_finish(e, d_out, base, plan_host[i], ids_out, st, drain, "the refined chain",
+                         strf("candidate (%d, %d) does not reach the goal: nothing appended", i, j).c_str());
 }
 
 // --------------------------------------------------------------------------------------------
-// Several plans per call: lqrrt_refine_search_multi / lqrrt_refine_commit_multi (refine_plans).  Per CHUNK of up to MULTI_MAX
-// engines: one image in device memory -- the keys, the commits' outputs and edge lengths, then a RefineDesc per engine and the
-// plans with their cost prefixes -- staged on the host, uploaded in one copy; one launch (refine.hpp k_refine_*_multi); the head
-// of the image (keys / outputs) back in one copy.  The chunks of a call are enqueued one after another and waited for once.
-// The image lives in a scratch of the chunk's first engine (d_refm: grown on demand, a few kB, like d_ref not part of the
-// footprint); the calls are synchronous, so nothing reads it after they return.
-struct RefineChunk {
-    int first = 0, n = 0;                 // engines [first, first + n) of the call
+// Several engines per call (refine_plans: lqrrt_refine_search_multi / lqrrt_refine_commit_multi; connect_goals and connect_vias
+// follow in their fragments).  Every argument of every engine is checked before anything is written or launched.  A call is cut
+// into CHUNKS of up to MULTI_MAX engines that take part (fewer than 2^32 threads per launch).  Per chunk: one image in device
+// memory -- what comes back at its head (a search's best keys; a commit's outputs and edge lengths), then a descriptor per engine
+// and the tables the descriptors point to -- staged on the host and uploaded in one copy; one launch; the head back in one copy.
+// The chunks of a call are enqueued one after another and waited for once.  The image lives in a scratch of the chunk's first
+// engine (d_refm: grown on demand, a few kB, like d_ref not part of the footprint); the calls are synchronous, so nothing reads it
+// after they return.  The host images are the sources and the targets of the copies: they outlive the call's synchronise, and a
+// call that fails drains the stream before they go (StreamDrain).
+struct MultiChunk {
+    int first = 0;                        // the engine (index into the call) whose scratch holds the image
     std::vector<int> members;             // indices (into the call) of the engines that take part in the launch
     std::vector<char> img;                // host image of the scratch
-    size_t o_out = 0, o_lens = 0, o_desc = 0, back = 0;
-    std::vector<size_t> lens_at;          // per member: its first edge length in the image (ints from o_lens)
+    size_t o_out = 0, o_lens = 0, back = 0;   // commit: the outputs [4] per member, the edge lengths, the bytes that come back
+    std::vector<size_t> lens_at;          // commit, per member: its first edge length (ints from o_lens)
+    int* out_of(char* image, size_t q) const { return (int*)(image + o_out) + 4 * q; }
+    int* lens_of(char* image, size_t q) const { return (int*)(image + o_lens) + lens_at[q]; }
 };
+
+// offsets into an image, each part 16-byte aligned
+struct Carve {
+    size_t off = 0;
+    size_t operator()(size_t bytes) { const size_t at = off; off += (bytes + 15) / 16 * 16; return at; }
+};
+
+// Cuts a call into chunks: groups[k] 64-thread workgroups for engine k (0: the engine takes part in no launch; a commit asks for
+// one per winner), up to MULTI_MAX members and fewer than 2^32 threads per chunk.
+static std::vector<MultiChunk> multi_chunks(const std::vector<long long>& groups) {
+    std::vector<MultiChunk> chunks;
+    long long sum = 0;
+    for (int k = 0; k < (int)groups.size(); ++k) {
+        if (groups[k] == 0) continue;
+        if (chunks.empty() || (int)chunks.back().members.size() == MULTI_MAX || (sum + groups[k]) * 64 > 0xffffffffLL) {
+            chunks.emplace_back();
+            chunks.back().first = k;
+            sum = 0;
+        }
+        chunks.back().members.push_back(k);
+        sum += groups[k];
+    }
+    return chunks;
+}
 
 static int refine_multi_scratch(lqrrt_engine* owner, size_t bytes, char** out) {
     if (bytes > owner->refm_cap) {
@@ -161,58 +265,28 @@ static int refine_multi_scratch(lqrrt_engine* owner, size_t bytes, char** out) {
     return 0;
 }
 
-// every argument of every engine, before anything is written or launched; bufs[k]: engine k's plan and cost prefix
-static int refine_multi_check(lqrrt_engine** engines, int n, const int32_t* const* plans, const int32_t* plan_lens, const int32_t* tries,
-                              const int32_t* horizons, std::vector<std::vector<int>>& bufs) {
+// The engine list of a call: up to 4 * MULTI_MAX distinct engines of one device and model, none generic; `args`: the call's other
+// arrays are all there; each(k): what the call asks of engine k, checked in the list's order.
+template <class Each>
+static int multi_engines_check(lqrrt_engine** engines, int n, bool args, Each each) {
     if (!engines || n < 1) return fail(LQRRT_E_ARG, "no engines");
-    if (!plans || !plan_lens || !tries || !horizons) return fail(LQRRT_E_ARG, "null argument");
+    if (!args) return fail(LQRRT_E_ARG, "null argument");
     if (n > 4 * MULTI_MAX) return fail(LQRRT_E_ARG, "at most %d engines per call", 4 * (int)MULTI_MAX);
-    lqrrt_engine* e0 = engines[0];
-    bufs.resize((size_t)n);
     for (int k = 0; k < n; ++k) {
         lqrrt_engine* e = engines[k];
         if (!e) return fail(LQRRT_E_ARG, "null engine");
         NOT_GENERIC(e);
         for (int q = 0; q < k; ++q)
             if (engines[q] == e) return fail(LQRRT_E_ARG, "engine %d appears twice", k);
-        if (e->device != e0->device || e->model != e0->model) return fail(LQRRT_E_ARG, "engines of one call share the device and the model");
-        TRY(refine_check(e, plans[k], plan_lens[k], tries[k], horizons[k], bufs[k]));
+        if (e->device != engines[0]->device || e->model != engines[0]->model)
+            return fail(LQRRT_E_ARG, "engines of one call share the device and the model");
+        TRY(each(k));
     }
     return 0;
 }
 
-// lays out a chunk's image and fills the descriptors of its members (a, best / out / lens); i, j, base are left to the caller
-static int refine_multi_stage(lqrrt_engine** engines, const std::vector<std::vector<int>>& bufs, const int32_t* plan_lens, const int32_t* tries,
-                              const int32_t* horizons, const std::vector<int>& ids_room, RefineChunk& c, char** d_img) {
-    const int m = (int)c.members.size();
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 15) / 16 * 16; return at; };
-    const size_t o_keys = carve(sizeof(unsigned long long) * m);
-    c.o_out = carve(sizeof(int) * 4 * m);
-    size_t sum_ids = 0;
-    c.lens_at.assign((size_t)m, 0);
-    for (int q = 0; q < m; ++q) { c.lens_at[q] = sum_ids; sum_ids += ids_room.empty() ? 0 : (size_t)ids_room[c.members[q]]; }
-    c.o_lens = carve(sizeof(int) * sum_ids);
-    c.back = off;
-    c.o_desc = carve(sizeof(RefineDesc) * m);
-    std::vector<size_t> o_plan((size_t)m);
-    for (int q = 0; q < m; ++q) o_plan[q] = carve(sizeof(int) * bufs[c.members[q]].size());
-    c.img.assign(off, 0);
-    TRY(refine_multi_scratch(engines[c.first], off, d_img));
-    RefineDesc* hd = (RefineDesc*)(c.img.data() + c.o_desc);
-    for (int q = 0; q < m; ++q) {
-        const int k = c.members[q];
-        memcpy(c.img.data() + o_plan[q], bufs[k].data(), sizeof(int) * bufs[k].size());
-        refine_fill_args(engines[k], (const int*)(*d_img + o_plan[q]), plan_lens[k], tries[k], horizons[k], &hd[q].a);
-        hd[q].best = (unsigned long long*)(*d_img + o_keys) + q;
-        hd[q].out = (int*)(*d_img + c.o_out) + 4 * q;
-        hd[q].lens = (int*)(*d_img + c.o_lens) + c.lens_at[q];
-        hd[q].i = hd[q].j = -1; hd[q].base = 0; hd[q].pad = 0;
-    }
-    return 0;
-}
-
-static int refine_multi_protos(lqrrt_engine** engines, const RefineChunk& c, const int32_t* horizons, hipStream_t st, ProtoTable& pt, size_t& lds) {
+// the prototypes of a chunk's members, current on the device, and the dynamic LDS of the launch that serves them all
+static int refine_multi_protos(lqrrt_engine** engines, const MultiChunk& c, const int32_t* horizons, hipStream_t st, ProtoTable& pt, size_t& lds) {
     memset(&pt, 0, sizeof pt);
     lds = 0;
     for (size_t q = 0; q < c.members.size(); ++q) {
@@ -224,63 +298,119 @@ static int refine_multi_protos(lqrrt_engine** engines, const RefineChunk& c, con
     return 0;
 }
 
-// A failed call: the caller still holds the chunks (their host images are the source or the target of copies that may be in
-// flight), so the stream is drained before they go.
-static int refine_multi_fail(int rc, hipStream_t st) {
-    const std::string keep = g_err;
-    (void)hipStreamSynchronize(st);
-    g_err = keep;
-    return rc;
+// the grid of a chunk's search: groups[k] workgroups for member k, the members side by side
+static unsigned multi_grid(const MultiChunk& c, const std::vector<long long>& groups, RetainGrid& gr) {
+    std::vector<long long> counts;
+    for (int k : c.members) counts.push_back(groups[k]);
+    return retain_grid(counts, gr);
+}
+
+// A search's image starts with one best key per member.  Waits for the call's chunks (its one synchronise) and returns every
+// engine's key: what its launch left, or its incumbent's where the engine took part in none.
+static int multi_search_keys(const std::vector<MultiChunk>& chunks, int n, const int64_t* incumbents, hipStream_t st, StreamDrain& drain,
+                             std::vector<unsigned long long>& keys) {
+    HIPCHK(hipStreamSynchronize(st));
+    drain.disarm();
+    keys.resize((size_t)n);
+    for (int k = 0; k < n; ++k) keys[k] = incumbent_key(incumbents[k]);
+    for (const MultiChunk& c : chunks)
+        for (size_t q = 0; q < c.members.size(); ++q) keys[c.members[q]] = ((const unsigned long long*)c.img.data())[q];
+    return 0;
+}
+
+// A commit's image starts with what comes back: out[4] per member (commit_finish's three, padded), then room[k] edge lengths for
+// every member k.
+static void multi_commit_head(MultiChunk& c, const std::vector<int>& room, Carve& carve) {
+    const size_t m = c.members.size();
+    c.o_out = carve(sizeof(int) * 4 * m);
+    size_t sum = 0;
+    c.lens_at.assign(m, 0);
+    for (size_t q = 0; q < m; ++q) { c.lens_at[q] = sum; sum += (size_t)room[c.members[q]]; }
+    c.o_lens = carve(sizeof(int) * sum);
+    c.back = carve.off;
+}
+
+// after the read-back of a commit's chunks: per member the refusal of its replay, or its new nodes below parent[k]
+static void multi_commit_adopt(lqrrt_engine** engines, std::vector<MultiChunk>& chunks, const std::vector<int>& parent, int32_t* const* ids_out,
+                               int32_t* counts_out) {
+    for (MultiChunk& c : chunks)
+        for (size_t q = 0; q < c.members.size(); ++q) {
+            const int k = c.members[q];
+            const int* out = c.out_of(c.img.data(), q);
+            if (out[0] < 0) { counts_out[k] = LQRRT_E_CAPACITY; continue; }
+            if (!out[2]) { counts_out[k] = LQRRT_E_STATE; continue; }      // (the chain does not reach the goal: nothing appended)
+            refine_adopt(engines[k], parent[k], out[0], c.lens_of(c.img.data(), q), ids_out[k]);
+            counts_out[k] = out[0];
+        }
+}
+
+// every argument of every engine, before anything is written or launched; bufs[k]: engine k's plan and cost prefix
+static int refine_multi_check(lqrrt_engine** engines, int n, const int32_t* const* plans, const int32_t* plan_lens, const int32_t* tries,
+                              const int32_t* horizons, std::vector<std::vector<int>>& bufs) {
+    return multi_engines_check(engines, n, plans && plan_lens && tries && horizons, [&](int k) {
+        bufs.emplace_back();
+        return refine_check(engines[k], plans[k], plan_lens[k], tries[k], horizons[k], bufs.back());
+    });
+}
+
+// behind the head of a chunk's image: a RefineDesc per member (a filled; what a search or a commit adds is left to the caller) and
+// the members' plans with their cost prefixes; allocates the image on both sides
+static int refine_multi_stage(lqrrt_engine** engines, const std::vector<std::vector<int>>& bufs, const int32_t* plan_lens, const int32_t* tries,
+                              const int32_t* horizons, MultiChunk& c, Carve& carve, char** d_img, size_t* o_desc) {
+    const int m = (int)c.members.size();
+    *o_desc = carve(sizeof(RefineDesc) * m);
+    std::vector<size_t> o_plan((size_t)m);
+    for (int q = 0; q < m; ++q) o_plan[q] = carve(sizeof(int) * bufs[c.members[q]].size());
+    c.img.assign(carve.off, 0);
+    TRY(refine_multi_scratch(engines[c.first], carve.off, d_img));
+    RefineDesc* hd = (RefineDesc*)(c.img.data() + *o_desc);
+    for (int q = 0; q < m; ++q) {
+        const int k = c.members[q];
+        memcpy(c.img.data() + o_plan[q], bufs[k].data(), sizeof(int) * bufs[k].size());
+        refine_fill_args(engines[k], (const int*)(*d_img + o_plan[q]), plan_lens[k], tries[k], horizons[k], &hd[q].a);
+        hd[q].i = hd[q].j = -1;
+    }
+    return 0;
 }
 
 static int refine_search_multi_run(lqrrt_engine** engines, int n, const std::vector<std::vector<int>>& bufs, const int32_t* plan_lens,
                                    const int32_t* tries, const int32_t* horizons, const int64_t* incumbents, int64_t* cost, int32_t* i_out,
-                                   int32_t* j_out, hipStream_t st, std::vector<RefineChunk>& chunks) {
-    // chunks: up to MULTI_MAX engines with candidates, one 64-thread workgroup per candidate and fewer than 2^32 threads per launch
-    long long cands = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long nc = (long long)plan_lens[k] * (plan_lens[k] - 1) / 2;
-        if (nc == 0) continue;
-        if (chunks.empty() || (int)chunks.back().members.size() == MULTI_MAX || (cands + nc) * 64 > 0xffffffffLL) {
-            chunks.emplace_back();
-            chunks.back().first = k;
-            cands = 0;
-        }
-        chunks.back().members.push_back(k);
-        cands += nc;
-    }
-    for (RefineChunk& c : chunks) {
+                                   int32_t* j_out, hipStream_t st) {
+    std::vector<long long> cands((size_t)n);
+    for (int k = 0; k < n; ++k) cands[k] = refine_candidates(plan_lens[k]);
+    std::vector<MultiChunk> chunks = multi_chunks(cands);
+    StreamDrain drain(st);
+    for (MultiChunk& c : chunks) {
         const int m = (int)c.members.size();
+        Carve carve;
+        carve(sizeof(unsigned long long) * m);                  // the keys
         char* d_img = nullptr;
-        TRY(refine_multi_stage(engines, bufs, plan_lens, tries, horizons, std::vector<int>(), c, &d_img));
-        unsigned long long* keys = (unsigned long long*)c.img.data();
-        std::vector<long long> counts((size_t)m);
+        size_t o_desc = 0;
+        TRY(refine_multi_stage(engines, bufs, plan_lens, tries, horizons, c, carve, &d_img, &o_desc));
+        RefineDesc* hd = (RefineDesc*)(c.img.data() + o_desc);
         for (int q = 0; q < m; ++q) {
-            const int k = c.members[q];
-            keys[q] = (unsigned long long)incumbents[k] << 32;  // (incumbent, 0, 0): every candidate at its cost loses
-            counts[q] = (long long)plan_lens[k] * (plan_lens[k] - 1) / 2;
+            ((unsigned long long*)c.img.data())[q] = incumbent_key(incumbents[c.members[q]]);
+            hd[q].best = (unsigned long long*)d_img + q;
         }
         ProtoTable pt;
         size_t lds = 0;
         TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
         RetainGrid gr;
-        const unsigned grid = retain_grid(counts, gr);
+        const unsigned grid = multi_grid(c, cands, gr);
+        drain.arm();
         HIPCHK(hipMemcpyAsync(d_img, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
         DISPATCH(engines[0], hipLaunchKernelGGL((k_refine_search_multi<S>), dim3(grid), dim3(64), lds, st, pt,
-                                                (const RefineDesc*)(d_img + c.o_desc), gr));
+                                                (const RefineDesc*)(d_img + o_desc), gr));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c.img.data(), d_img, sizeof(unsigned long long) * m, hipMemcpyDeviceToHost, st));
     }
-    HIPCHK(hipStreamSynchronize(st));
-    for (const RefineChunk& c : chunks) {
-        const unsigned long long* keys = (const unsigned long long*)c.img.data();
-        for (size_t q = 0; q < c.members.size(); ++q) {
-            const int k = c.members[q];
-            if (keys[q] == (unsigned long long)incumbents[k] << 32) continue;
-            cost[k] = (int64_t)(keys[q] >> 32);
-            i_out[k] = (int32_t)((keys[q] >> 16) & 0xffff);
-            j_out[k] = (int32_t)(keys[q] & 0xffff);
-        }
+    std::vector<unsigned long long> keys;
+    TRY(multi_search_keys(chunks, n, incumbents, st, drain, keys));
+    for (int k = 0; k < n; ++k) {
+        if (keys[k] == incumbent_key(incumbents[k])) continue;
+        cost[k] = (int64_t)(keys[k] >> 32);
+        i_out[k] = (int32_t)((keys[k] >> 16) & 0xffff);
+        j_out[k] = (int32_t)(keys[k] & 0xffff);
     }
     return 0;
 }
@@ -292,65 +422,57 @@ extern "C" int lqrrt_refine_search_multi(lqrrt_engine** engines, int n, const in
     TRY(refine_multi_check(engines, n, plans, plan_lens, goal_tries, horizon_iters, bufs));
     if (!incumbents || !cost_out || !i_out || !j_out) return fail(LQRRT_E_ARG, "null argument");
     for (int k = 0; k < n; ++k) {
-        if (incumbents[k] < 1 || incumbents[k] > 0x7fffffffLL)
-            return fail(LQRRT_E_ARG, "incumbent cost %lld out of range (engine %d)", (long long)incumbents[k], k);
-        if ((long long)plan_lens[k] * (plan_lens[k] - 1) / 2 * 64 > 0xffffffffLL)
-            return fail(LQRRT_E_ARG, "plan of %d nodes: %lld candidates exceed one launch (at most 11586 nodes)", plan_lens[k],
-                        (long long)plan_lens[k] * (plan_lens[k] - 1) / 2);
+        TRY(incumbent_check(incumbents[k], k));
+        TRY(refine_candidates_check(plan_lens[k]));
     }
     TRY(use_device(engines[0]));
-    hipStream_t st = (hipStream_t)stream;
     for (int k = 0; k < n; ++k) { cost_out[k] = incumbents[k]; i_out[k] = -1; j_out[k] = -1; }
-    std::vector<RefineChunk> chunks;                            // (outlives every copy of the call, also when the call fails)
-    const int rc = refine_search_multi_run(engines, n, bufs, plan_lens, goal_tries, horizon_iters, incumbents, cost_out, i_out, j_out, st, chunks);
-    return rc ? refine_multi_fail(rc, st) : 0;
+    return refine_search_multi_run(engines, n, bufs, plan_lens, goal_tries, horizon_iters, incumbents, cost_out, i_out, j_out, (hipStream_t)stream);
 }
 
+// The replay of one candidate (ci[k], cj[k]) per engine with a winner (ci[k] >= 0), one workgroup each.  connect_goals' commit is
+// this one too: per winner the one-node plan [v] with the cost prefix [depth[v]] and the candidate (0, 0).
 static int refine_commit_multi_run(lqrrt_engine** engines, int n, const std::vector<std::vector<int>>& bufs, const int32_t* plan_lens,
                                    const int32_t* tries, const int32_t* horizons, const int32_t* ci, const int32_t* cj, int32_t* const* ids_out,
-                                   int32_t* counts_out, hipStream_t st, std::vector<RefineChunk>& chunks) {
-    std::vector<int> room((size_t)n, 0);
+                                   int32_t* counts_out, hipStream_t st) {
+    std::vector<int> room((size_t)n, 0), parent((size_t)n, -1);
+    std::vector<long long> winner((size_t)n, 0);
     for (int k = 0; k < n; ++k) {
         counts_out[k] = 0;
         if (ci[k] < 0) continue;                                // (no winner: not part of the launch)
         room[k] = plan_lens[k] - 1 - cj[k] + tries[k];
-        if (chunks.empty() || (int)chunks.back().members.size() == MULTI_MAX) {
-            chunks.emplace_back();
-            chunks.back().first = k;
-        }
-        chunks.back().members.push_back(k);
+        parent[k] = bufs[k][(size_t)ci[k]];
+        winner[k] = 1;
     }
-    for (RefineChunk& c : chunks) {
+    std::vector<MultiChunk> chunks = multi_chunks(winner);
+    StreamDrain drain(st);
+    for (MultiChunk& c : chunks) {
         const int m = (int)c.members.size();
+        Carve carve;
+        multi_commit_head(c, room, carve);
         char* d_img = nullptr;
-        TRY(refine_multi_stage(engines, bufs, plan_lens, tries, horizons, room, c, &d_img));
-        RefineDesc* hd = (RefineDesc*)(c.img.data() + c.o_desc);
+        size_t o_desc = 0;
+        TRY(refine_multi_stage(engines, bufs, plan_lens, tries, horizons, c, carve, &d_img, &o_desc));
+        RefineDesc* hd = (RefineDesc*)(c.img.data() + o_desc);
         for (int q = 0; q < m; ++q) {
             const int k = c.members[q];
+            hd[q].out = c.out_of(d_img, q);
+            hd[q].lens = c.lens_of(d_img, q);
             hd[q].i = ci[k]; hd[q].j = cj[k]; hd[q].base = engines[k]->N;
         }
         ProtoTable pt;
         size_t lds = 0;
         TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
+        drain.arm();
         HIPCHK(hipMemcpyAsync(d_img, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
         DISPATCH(engines[0], hipLaunchKernelGGL((k_refine_commit_multi<S>), dim3((unsigned)m), dim3(64), lds, st, pt,
-                                                (const RefineDesc*)(d_img + c.o_desc), m));
+                                                (const RefineDesc*)(d_img + o_desc), m));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c.img.data(), d_img, c.back, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
-    for (const RefineChunk& c : chunks) {
-        const int* outs = (const int*)(c.img.data() + c.o_out);
-        const int* lens = (const int*)(c.img.data() + c.o_lens);
-        for (size_t q = 0; q < c.members.size(); ++q) {
-            const int k = c.members[q];
-            const int* out = outs + 4 * q;
-            if (out[0] < 0) { counts_out[k] = LQRRT_E_CAPACITY; continue; }
-            if (!out[2]) { counts_out[k] = LQRRT_E_STATE; continue; }      // (the chain does not reach the goal: nothing appended)
-            refine_adopt(engines[k], bufs[k][(size_t)ci[k]], out[0], lens + c.lens_at[q], ids_out[k]);
-            counts_out[k] = out[0];
-        }
-    }
+    drain.disarm();
+    multi_commit_adopt(engines, chunks, parent, ids_out, counts_out);
     return 0;
 }
 
@@ -369,8 +491,5 @@ extern "C" int lqrrt_refine_commit_multi(lqrrt_engine** engines, int n, const in
             return fail(LQRRT_E_ARG, "ids_out of engine %d must hold %d ids", k, P - 1 - j[k] + goal_tries[k]);
     }
     TRY(use_device(engines[0]));
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<RefineChunk> chunks;                            // (outlives every copy of the call, also when the call fails)
-    const int rc = refine_commit_multi_run(engines, n, bufs, plan_lens, goal_tries, horizon_iters, i, j, ids_out, counts_out, st, chunks);
-    return rc ? refine_multi_fail(rc, st) : 0;
+    return refine_commit_multi_run(engines, n, bufs, plan_lens, goal_tries, horizon_iters, i, j, ids_out, counts_out, (hipStream_t)stream);
 }

@@ -470,18 +470,67 @@ class Engine(object):
                                                     nat.ptr(out), len(out), self._stream()))
         return out[:k].tolist()
 
+    # What the wrappers of the refine, connect, via and reach calls share: how an argument of theirs becomes what the native call
+    # takes.  The arrays they return are what the pointers point into: the caller holds them until the native call has returned.
+    @staticmethod
+    def _id_list(nodes, unique=False):
+        """(ids, pointer, count) of a candidate id list: (None, None, 0) for None (every node), else a flat int32 array -- `unique`:
+        sorted and freed of duplicates."""
+        if nodes is None:
+            return None, None, 0
+        ids = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        if unique:
+            ids = np.unique(ids)
+        return ids, nat.ptr(ids), len(ids)
+
+    @staticmethod
+    def _per_engine(values, n, what):
+        values = list(values)
+        if len(values) != n:
+            raise ValueError("expected one %s per engine" % what)
+        return values
+
+    @staticmethod
+    def _id_lists(nodes, n, unique=False):
+        """(arrays, pointers, pointer to the counts) of one id list (or None) per engine, each as _id_list makes it; (None, None,
+        None) for None."""
+        if nodes is None:
+            return None, None, None
+        ids = [Engine._id_list(v, unique)[0] for v in Engine._per_engine(nodes, n, "id list (or None)")]
+        counts = np.ascontiguousarray([0 if a is None else len(a) for a in ids], dtype=np.int32)
+        ids = [a if a is None or len(a) else np.zeros(1, dtype=np.int32) for a in ids]    # (an empty list still has an address)
+        return (ids, counts), (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in ids]), nat.ptr(counts)
+
+    @staticmethod
+    def _incumbents(incumbents, n, what="engine"):
+        inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
+        if inc.shape != (n,):
+            raise ValueError("expected one incumbent per %s" % what)
+        return inc
+
+    @staticmethod
+    def _commit_outputs(rooms):
+        """(outs, pointers, capacities, counts) of a commit for several engines: room for rooms[k] new ids of engine k."""
+        outs = [np.empty(max(int(r), 1), dtype=np.int32) for r in rooms]
+        out_ptrs = (C.c_void_p * len(outs))(*[a.ctypes.data for a in outs])
+        return outs, out_ptrs, np.ascontiguousarray([len(a) for a in outs], dtype=np.int32), np.zeros(len(outs), dtype=np.int32)
+
+    @staticmethod
+    def _commit_results(outs, counts, message):
+        """What a commit for several engines returns: per engine the new ids, None where the tree is full.  An engine whose chain
+        fell short raises NativeError -- message(k) for the first such k -- that carries what the others committed."""
+        results = [None if counts[k] < 0 else outs[k][:counts[k]].tolist() for k in range(len(outs))]
+        bad = [k for k in range(len(outs)) if counts[k] < 0 and counts[k] != nat.E_CAPACITY]
+        if bad:
+            err = nat.NativeError(int(counts[bad[0]]), message(bad[0]))
+            err.results, err.failed = results, bad                  # what the other engines of the call committed
+            raise err
+        return results
+
     @staticmethod
     def _refine_multi_args(engines, plans, horizons, goal_tries):
-        engines = list(engines)
-        n = len(engines)
-        if n < 1:
-            raise ValueError("no engines")
-        plans = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in plans]
-        horizons = np.ascontiguousarray([int(h) for h in horizons], dtype=np.int32)
-        tries = np.ascontiguousarray(np.broadcast_to(np.asarray(goal_tries, dtype=np.int64), (n,)), dtype=np.int32)
-        if len(plans) != n or horizons.shape != (n,):
-            raise ValueError("expected one plan and one horizon per engine")
-        handles = (C.c_void_p * n)(*[e.h for e in engines])
+        engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
+        plans = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in Engine._per_engine(plans, n, "plan")]
         plan_ptrs = (C.c_void_p * n)(*[p.ctypes.data for p in plans])
         plan_lens = np.ascontiguousarray([len(p) for p in plans], dtype=np.int32)
         return engines, n, handles, plans, plan_ptrs, plan_lens, horizons, tries
@@ -493,9 +542,7 @@ class Engine(object):
         all or one per engine.  Returns [(cost, i, j) or None] in the engines' order, each what that engine's own refine_round
         returns.  The engines share device and model; every argument is checked before anything is launched."""
         engines, n, handles, plans, plan_ptrs, plan_lens, horizons, tries = Engine._refine_multi_args(engines, plans, horizons, goal_tries)
-        inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
-        if inc.shape != (n,):
-            raise ValueError("expected one incumbent per engine")
+        inc = Engine._incumbents(incumbents, n)
         cost, i, j = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
         nat.check(nat.lib().lqrrt_refine_search_multi(handles, n, plan_ptrs, nat.ptr(plan_lens), nat.ptr(tries), nat.ptr(horizons),
                                                       nat.ptr(inc), nat.ptr(cost), nat.ptr(i), nat.ptr(j), engines[0]._stream()))
@@ -509,36 +556,24 @@ class Engine(object):
         does not reach the goal raises NativeError(E_STATE) after the other engines have committed; the error carries what they
         appended (`results`: this list, `failed`: the indices of the engines that appended nothing for that reason)."""
         engines, n, handles, plans, plan_ptrs, plan_lens, horizons, tries = Engine._refine_multi_args(engines, plans, horizons, goal_tries)
-        ijs = list(ijs)
-        if len(ijs) != n:
-            raise ValueError("expected one candidate per engine")
+        ijs = Engine._per_engine(ijs, n, "candidate")
         ci = np.ascontiguousarray([-1 if c is None else int(c[0]) for c in ijs], dtype=np.int32)
         cj = np.ascontiguousarray([-1 if c is None else int(c[1]) for c in ijs], dtype=np.int32)
-        outs = [np.empty(max(len(plans[k]) - 1 - max(int(cj[k]), 0) + int(tries[k]), 1), dtype=np.int32) for k in range(n)]
-        out_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs])
-        caps = np.ascontiguousarray([len(a) for a in outs], dtype=np.int32)
-        counts = np.zeros(n, dtype=np.int32)
+        outs, out_ptrs, caps, counts = Engine._commit_outputs(len(plans[k]) - 1 - max(int(cj[k]), 0) + int(tries[k]) for k in range(n))
         nat.check(nat.lib().lqrrt_refine_commit_multi(handles, n, plan_ptrs, nat.ptr(plan_lens), nat.ptr(tries), nat.ptr(horizons),
                                                       nat.ptr(ci), nat.ptr(cj), out_ptrs, nat.ptr(caps), nat.ptr(counts),
                                                       engines[0]._stream()))
-        results = [None if counts[k] < 0 else outs[k][:counts[k]].tolist() for k in range(n)]
-        bad = [k for k in range(n) if counts[k] < 0 and counts[k] != nat.E_CAPACITY]
-        if bad:
-            err = nat.NativeError(int(counts[bad[0]]), "candidate (%d, %d) of engine %d does not reach the goal: nothing appended"
-                                  % (ci[bad[0]], cj[bad[0]], bad[0]))
-            err.results, err.failed = results, bad                  # what the other engines of the call committed
-            raise err
-        return results
+        return Engine._commit_results(outs, counts, lambda k: "candidate (%d, %d) of engine %d does not reach the goal: nothing appended"
+                                      % (ci[k], cj[k], k))
 
     # -- tree-wide goal connection (csrc/engine_connect.hpp; the rule: tests/connect_reference.py) ---------
     def connect_search(self, horizon_iters, incumbent, goal_tries=8, nodes=None):
         """(cost, node) of the tree node -- any node, or one of `nodes` -- whose chain of up to `goal_tries` steers toward the goal
         reaches it in the fewest steps from the root, fewer than `incumbent`; None when there is none (lqrrt_connect_search)."""
-        ids = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        ids, ids_ptr, count = self._id_list(nodes)
         cost, node = C.c_int64(), C.c_int32()
-        nat.check(nat.lib().lqrrt_connect_search(self.h, None if ids is None else nat.ptr(ids), 0 if ids is None else len(ids),
-                                                 int(goal_tries), int(horizon_iters), int(incumbent), C.byref(cost), C.byref(node),
-                                                 self._stream()))
+        nat.check(nat.lib().lqrrt_connect_search(self.h, ids_ptr, count, int(goal_tries), int(horizon_iters), int(incumbent),
+                                                 C.byref(cost), C.byref(node), self._stream()))
         return None if node.value < 0 else (cost.value, node.value)
 
     def connect_commit(self, node, horizon_iters, goal_tries=8):
@@ -573,15 +608,10 @@ class Engine(object):
         beat).  The engine's own goal is not involved, and nothing of the engine changes."""
         goals, lo, hi = self._targets(goals, buffers)
         T = len(goals)
-        ids = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
-        inc = None
-        if incumbents is not None:
-            inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
-            if inc.shape != (T,):
-                raise ValueError("expected one incumbent per goal")
+        ids, ids_ptr, count = self._id_list(nodes)
+        inc = None if incumbents is None else self._incumbents(incumbents, T, "goal")
         cost, node = np.empty(max(T, 1), dtype=np.int64), np.empty(max(T, 1), dtype=np.int32)
-        nat.check(nat.lib().lqrrt_reach_search(self.h, nat.ptr(goals), nat.ptr(lo), nat.ptr(hi), T,
-                                               None if ids is None else nat.ptr(ids), 0 if ids is None else len(ids), int(goal_tries),
+        nat.check(nat.lib().lqrrt_reach_search(self.h, nat.ptr(goals), nat.ptr(lo), nat.ptr(hi), T, ids_ptr, count, int(goal_tries),
                                                int(horizon_iters), None if inc is None else nat.ptr(inc), nat.ptr(cost), nat.ptr(node),
                                                self._stream()))
         return [None if node[t] < 0 else (int(cost[t]), int(node[t])) for t in range(T)]
@@ -612,11 +642,11 @@ class Engine(object):
         (lqrrt_connect_via_search).  j = len(waypoints) is connect_search's candidate.  An id list is sorted and its duplicates are
         removed: the winner does not depend on its order."""
         way = self._waypoints(waypoints)
-        ids = None if nodes is None else np.unique(np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1))
+        ids, ids_ptr, count = self._id_list(nodes, unique=True)
         cost, node, j = C.c_int64(), C.c_int32(), C.c_int32()
-        nat.check(nat.lib().lqrrt_connect_via_search(self.h, None if ids is None else nat.ptr(ids), 0 if ids is None else len(ids),
-                                                     nat.ptr(way) if len(way) else None, len(way), int(goal_tries), int(horizon_iters),
-                                                     int(incumbent), C.byref(cost), C.byref(node), C.byref(j), self._stream()))
+        nat.check(nat.lib().lqrrt_connect_via_search(self.h, ids_ptr, count, nat.ptr(way) if len(way) else None, len(way),
+                                                     int(goal_tries), int(horizon_iters), int(incumbent), C.byref(cost),
+                                                     C.byref(node), C.byref(j), self._stream()))
         return None if node.value < 0 else (cost.value, node.value, j.value)
 
     def connect_via_commit(self, node, j, waypoints, horizon_iters, goal_tries=8):
@@ -650,22 +680,11 @@ class Engine(object):
         Returns [(cost, node) or None] in the engines' order, each what that engine's own connect_search returns.  The engines share
         device and model; every argument is checked before anything is launched."""
         engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
-        inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
-        if inc.shape != (n,):
-            raise ValueError("expected one incumbent per engine")
-        node_ptrs = counts = None
-        if nodes is not None:
-            nodes = list(nodes)
-            if len(nodes) != n:
-                raise ValueError("expected one id list (or None) per engine")
-            ids = [None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in nodes]
-            counts = np.ascontiguousarray([0 if a is None else len(a) for a in ids], dtype=np.int32)
-            ids = [a if a is None or len(a) else np.zeros(1, dtype=np.int32) for a in ids]    # (an empty list still has an address)
-            node_ptrs = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in ids])
+        inc = Engine._incumbents(incumbents, n)
+        ids, node_ptrs, counts_ptr = Engine._id_lists(nodes, n)
         cost, node = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
-        nat.check(nat.lib().lqrrt_connect_search_multi(handles, n, node_ptrs, None if counts is None else nat.ptr(counts), nat.ptr(tries),
-                                                       nat.ptr(horizons), nat.ptr(inc), nat.ptr(cost), nat.ptr(node),
-                                                       engines[0]._stream()))
+        nat.check(nat.lib().lqrrt_connect_search_multi(handles, n, node_ptrs, counts_ptr, nat.ptr(tries), nat.ptr(horizons), nat.ptr(inc),
+                                                       nat.ptr(cost), nat.ptr(node), engines[0]._stream()))
         return [None if node[k] < 0 else (int(cost[k]), int(node[k])) for k in range(n)]
 
     @staticmethod
@@ -676,34 +695,21 @@ class Engine(object):
         reach the goal raises NativeError(E_STATE) after the other engines have committed; the error carries what they appended
         (`results`: this list, `failed`: the indices of the engines that appended nothing for that reason)."""
         engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
-        nodes = list(nodes)
-        if len(nodes) != n:
-            raise ValueError("expected one candidate per engine")
+        nodes = Engine._per_engine(nodes, n, "candidate")
         if any(v is not None and int(v) < 0 for v in nodes):
             raise ValueError("a candidate is a node id >= 0, or None")
         cn = np.ascontiguousarray([-1 if v is None else int(v) for v in nodes], dtype=np.int32)
-        outs = [np.empty(max(int(tries[k]), 1), dtype=np.int32) for k in range(n)]
-        out_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs])
-        caps = np.ascontiguousarray([len(a) for a in outs], dtype=np.int32)
-        counts = np.zeros(n, dtype=np.int32)
+        outs, out_ptrs, caps, counts = Engine._commit_outputs(tries)
         nat.check(nat.lib().lqrrt_connect_commit_multi(handles, n, nat.ptr(cn), nat.ptr(tries), nat.ptr(horizons), out_ptrs, nat.ptr(caps),
                                                        nat.ptr(counts), engines[0]._stream()))
-        results = [None if counts[k] < 0 else outs[k][:counts[k]].tolist() for k in range(n)]
-        bad = [k for k in range(n) if counts[k] < 0 and counts[k] != nat.E_CAPACITY]
-        if bad:
-            err = nat.NativeError(int(counts[bad[0]]), "the chain below node %d of engine %d does not reach the goal: nothing appended"
-                                  % (cn[bad[0]], bad[0]))
-            err.results, err.failed = results, bad                  # what the other engines of the call committed
-            raise err
-        return results
+        return Engine._commit_results(outs, counts, lambda k: "the chain below node %d of engine %d does not reach the goal: nothing appended"
+                                      % (cn[k], k))
 
     # -- goal chains through waypoints for several trees per call (csrc/engine_connect_via_multi.hpp) ---------
     @staticmethod
     def _waypoints_multi(engines, waypoints):
         """One table [Q][n] per engine (None or empty: Q = 0), the array of their addresses and their lengths."""
-        waypoints = list(waypoints)
-        if len(waypoints) != len(engines):
-            raise ValueError("expected one waypoint table (or None) per engine")
+        waypoints = Engine._per_engine(waypoints, len(engines), "waypoint table (or None)")
         ways = [e._waypoints(() if w is None else w) for e, w in zip(engines, waypoints)]
         ptrs = (C.c_void_p * len(ways))(*[w.ctypes.data if len(w) else None for w in ways])
         return ways, ptrs, np.ascontiguousarray([len(w) for w in ways], dtype=np.int32)
@@ -719,22 +725,12 @@ class Engine(object):
         argument is checked before anything is launched."""
         engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
         ways, way_ptrs, Q = Engine._waypoints_multi(engines, waypoints)
-        inc = np.ascontiguousarray([int(c) for c in incumbents], dtype=np.int64)
-        if inc.shape != (n,):
-            raise ValueError("expected one incumbent per engine")
-        node_ptrs = counts = None
-        if nodes is not None:
-            nodes = list(nodes)
-            if len(nodes) != n:
-                raise ValueError("expected one id list (or None) per engine")
-            ids = [None if v is None else np.unique(np.ascontiguousarray(v, dtype=np.int32).reshape(-1)) for v in nodes]
-            counts = np.ascontiguousarray([0 if a is None else len(a) for a in ids], dtype=np.int32)
-            ids = [a if a is None or len(a) else np.zeros(1, dtype=np.int32) for a in ids]    # (an empty list still has an address)
-            node_ptrs = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in ids])
+        inc = Engine._incumbents(incumbents, n)
+        ids, node_ptrs, counts_ptr = Engine._id_lists(nodes, n, unique=True)
         cost, node, j = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
-        nat.check(nat.lib().lqrrt_connect_via_search_multi(handles, n, node_ptrs, None if counts is None else nat.ptr(counts), way_ptrs,
-                                                           nat.ptr(Q), nat.ptr(tries), nat.ptr(horizons), nat.ptr(inc), nat.ptr(cost),
-                                                           nat.ptr(node), nat.ptr(j), engines[0]._stream()))
+        nat.check(nat.lib().lqrrt_connect_via_search_multi(handles, n, node_ptrs, counts_ptr, way_ptrs, nat.ptr(Q), nat.ptr(tries),
+                                                           nat.ptr(horizons), nat.ptr(inc), nat.ptr(cost), nat.ptr(node), nat.ptr(j),
+                                                           engines[0]._stream()))
         return [None if node[k] < 0 else (int(cost[k]), int(node[k]), int(j[k])) for k in range(n)]
 
     @staticmethod
@@ -747,28 +743,17 @@ class Engine(object):
         reason)."""
         engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
         ways, way_ptrs, Q = Engine._waypoints_multi(engines, waypoints)
-        candidates = list(candidates)
-        if len(candidates) != n:
-            raise ValueError("expected one candidate per engine")
+        candidates = Engine._per_engine(candidates, n, "candidate")
         if any(c is not None and (int(c[0]) < 0 or int(c[1]) < 0) for c in candidates):
             raise ValueError("a candidate is a pair (node id >= 0, first waypoint >= 0), or None")
         cn = np.ascontiguousarray([-1 if c is None else int(c[0]) for c in candidates], dtype=np.int32)
         cj = np.ascontiguousarray([-1 if c is None else int(c[1]) for c in candidates], dtype=np.int32)
-        outs = [np.empty(max(int(Q[k]) + int(tries[k]), 1), dtype=np.int32) for k in range(n)]
-        out_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in outs])
-        caps = np.ascontiguousarray([len(a) for a in outs], dtype=np.int32)
-        counts = np.zeros(n, dtype=np.int32)
+        outs, out_ptrs, caps, counts = Engine._commit_outputs(int(Q[k]) + int(tries[k]) for k in range(n))
         nat.check(nat.lib().lqrrt_connect_via_commit_multi(handles, n, nat.ptr(cn), nat.ptr(cj), way_ptrs, nat.ptr(Q), nat.ptr(tries),
                                                            nat.ptr(horizons), out_ptrs, nat.ptr(caps), nat.ptr(counts),
                                                            engines[0]._stream()))
-        results = [None if counts[k] < 0 else outs[k][:counts[k]].tolist() for k in range(n)]
-        bad = [k for k in range(n) if counts[k] < 0 and counts[k] != nat.E_CAPACITY]
-        if bad:
-            err = nat.NativeError(int(counts[bad[0]]), "the chain of candidate (%d, %d) of engine %d does not reach the goal: nothing appended"
-                                  % (cn[bad[0]], cj[bad[0]], bad[0]))
-            err.results, err.failed = results, bad                  # what the other engines of the call committed
-            raise err
-        return results
+        return Engine._commit_results(outs, counts, lambda k: "the chain of candidate (%d, %d) of engine %d does not reach the goal: "
+                                      "nothing appended" % (cn[k], cj[k], k))
 
     def push_samples(self, xs):
         xs = nat.as_f64(xs)

@@ -595,11 +595,7 @@ class Planner:
         fallback plan has none).  Returns True when the plan was replaced; False, with everything unchanged, when there is no tree
         of this planner on the device, no chain is shorter, or the tree cannot hold the winner's chain.
         """
-        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
-            raise NotImplementedError("connect_goal: in callback mode the steer is the user's Python function, which every candidate "
-                                      "of the search would have to run; the device cannot call it.")
-        if int(goal_tries) < 1:
-            raise ValueError("goal_tries must be >= 1.")
+        self._device_search_check("connect_goal", goal_tries)
         run = self._connect_begin()
         if run is None:
             return False
@@ -608,12 +604,9 @@ class Planner:
         if win is None:
             return False
         cost, node = win
-        try:
-            ids = eng.connect_commit(node, run.H, goal_tries)
-        except nat.NativeError as ex:
-            if ex.code == nat.E_CAPACITY:
-                return False
-            raise
+        ids = self._commit_winner(lambda: eng.connect_commit(node, run.H, goal_tries))
+        if ids is None:
+            return False
         self._connect_accept(run, cost, node, ids, finish_on_goal)
         return True
 
@@ -638,11 +631,7 @@ class Planner:
 
         Return value, refusals, `finish_on_goal` and plan_reached_goal are connect_goal's.  refine_plan() may follow.
         """
-        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
-            raise NotImplementedError("connect_via: in callback mode the steer is the user's Python function, which every candidate "
-                                      "of the search would have to run; the device cannot call it.")
-        if int(goal_tries) < 1:
-            raise ValueError("goal_tries must be >= 1.")
+        self._device_search_check("connect_via", goal_tries)
         way = np.ascontiguousarray(waypoints, dtype=np.float64)
         if way.size == 0 and way.ndim <= 2:
             way = way.reshape(0, self.nstates)
@@ -656,12 +645,9 @@ class Planner:
         if win is None:
             return False
         cost, node, j = win
-        try:
-            ids = eng.connect_via_commit(node, j, way, run.H, goal_tries)
-        except nat.NativeError as ex:
-            if ex.code == nat.E_CAPACITY:
-                return False
-            raise
+        ids = self._commit_winner(lambda: eng.connect_via_commit(node, j, way, run.H, goal_tries))
+        if ids is None:
+            return False
         self._connect_accept(run, cost, node, ids, finish_on_goal)
         return True
 
@@ -676,7 +662,26 @@ class Planner:
 
     # The steps of a goal connection that connect_goal (one planner, its engine's own calls) and connect_goals (a fleet, batched
     # calls) share: what is searched, what the search has to beat, what a committed winner changes.  They go through the
-    # refinement's own steps.
+    # refinement's own steps.  connect_via, goal_costs and retarget go through them too.
+    def _device_search_check(self, name, goal_tries):
+        """What the device searches refuse alike, before they look at the tree."""
+        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
+            raise NotImplementedError("%s: in callback mode the steer is the user's Python function, which every candidate "
+                                      "of the search would have to run; the device cannot call it." % name)
+        if int(goal_tries) < 1:
+            raise ValueError("goal_tries must be >= 1.")
+
+    @staticmethod
+    def _commit_winner(commit):
+        """The new node ids of commit(), a search's winner replayed into the tree; None, with the tree unchanged, when it cannot
+        hold the chain."""
+        try:
+            return commit()
+        except nat.NativeError as ex:
+            if ex.code == nat.E_CAPACITY:
+                return None
+            raise
+
     def _connect_begin(self):
         """The connection's state (_RefineRun), or None when there is no tree of this planner on the device.  Reads only."""
         run = self._refine_begin(need_goal=False)
@@ -735,11 +740,7 @@ class Planner:
         planner.goal currently is nor on whether the plan reached it.  Returns None when there is no tree of this planner on the
         device (refine_plan's condition).  retarget(goals[t]) then makes goal t the planner's.
         """
-        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
-            raise NotImplementedError("goal_costs: in callback mode the steer is the user's Python function, which every candidate "
-                                      "of the search would have to run; the device cannot call it.")
-        if int(goal_tries) < 1:
-            raise ValueError("goal_tries must be >= 1.")
+        self._device_search_check("goal_costs", goal_tries)
         goals = np.ascontiguousarray(goals, dtype=np.float64)
         if goals.ndim != 2 or goals.shape[1] != self.nstates or len(goals) < 1:
             raise ValueError("Expected goals of shape (T, %d) with T >= 1." % self.nstates)
@@ -768,11 +769,7 @@ class Planner:
         this planner on the device, no chain reaches the goal, or the tree cannot hold the winner's chain.  With the goal the tree
         was grown for -- when it still is the planner's -- this is connect_goal, which replaces a plan only with a shorter one.
         """
-        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
-            raise NotImplementedError("retarget: in callback mode the steer is the user's Python function, which every candidate "
-                                      "of the search would have to run; the device cannot call it.")
-        if int(goal_tries) < 1:
-            raise ValueError("goal_tries must be >= 1.")
+        self._device_search_check("retarget", goal_tries)
         goal = np.array(goal, dtype=np.float64)
         if goal.shape != (self.nstates,):
             raise ValueError("The goal state must have same dimensionality as state space.")
@@ -786,12 +783,9 @@ class Planner:
         if win is None:
             return False
         cost, node = win
-        try:
-            ids = eng.reach_commit(goal, buff, node, run.H, goal_tries)
-        except nat.NativeError as ex:
-            if ex.code == nat.E_CAPACITY:
-                return False
-            raise
+        ids = self._commit_winner(lambda: eng.reach_commit(goal, buff, node, run.H, goal_tries))
+        if ids is None:
+            return False
         self.set_goal(goal)
         self._engine_resolution(eng)                                # (the horizon is the tree's: the tree stays)
         self._grown_goal = np.array(self.goal, dtype=np.float64)
@@ -1112,6 +1106,56 @@ def _add_stats(a, b):
     return out
 
 
+# What refine_plans, connect_vias and connect_goals share: who may take part, which planners share a native call, and what a commit
+# call leaves behind when one of its engines fails.
+def _fleet_check(name, planners, goal_tries, nodes=None):
+    """Refuses, before any planner is touched: goal_tries < 1, a `nodes` sequence of the wrong length, a planner that appears twice,
+    an object that is not a Planner, a callback-mode planner."""
+    if int(goal_tries) < 1:
+        raise ValueError("goal_tries must be >= 1.")
+    if nodes is not None and len(nodes) != len(planners):
+        raise ValueError("%s: expected one id list (or None) per planner." % name)
+    if len(set(id(p) for p in planners)) != len(planners):
+        raise ValueError("%s: a planner appears twice." % name)
+    for p in planners:
+        if not isinstance(p, Planner):
+            raise ValueError("%s: expected Planner objects." % name)
+        if p.callback_mode:                                         # (as the last set_system left it, as in the planner's own method)
+            raise ValueError("%s: planners whose plugins are Python callables cannot take part (the device cannot call them)." % name)
+
+
+def _fleet_begin(name, planners, begin):
+    """begin(p) of every planner -- its _RefineRun, or None when it takes part in no launch; what the planner's own method refuses
+    with RuntimeError is a ValueError here, raised before any planner is touched."""
+    try:
+        return [begin(p) for p in planners]
+    except RuntimeError as ex:
+        raise ValueError(str(ex).replace("refine_plan:", name + ":").replace("connect_goal:", name + ":"))
+
+
+def _fleet_groups(planners, runs):
+    """The planners (their indices) that share a native call: those with a run, of one (device, native system type), in slices of
+    128 (a native call takes at most 128 engines); groups in the order of their first members."""
+    groups = {}
+    for k, (p, run) in enumerate(zip(planners, runs)):
+        if run is not None:
+            groups.setdefault((p.device, type(p.system)), []).append(k)
+    for members in groups.values():
+        for first in range(0, len(members), 128):
+            yield members[first:first + 128]
+
+
+def _fleet_commit(commit):
+    """(new ids per engine, error) of commit(), a commit call for several engines: when it fails after some of its engines did
+    commit, their results are kept (their plans follow) and the error is handed back to be raised once they are adopted."""
+    try:
+        return commit(), None
+    except nat.NativeError as ex:
+        if getattr(ex, "results", None) is None:
+            raise
+        return ex.results, ex
+
+
 def refine_plans(planners, max_rounds=8, goal_tries=8):
     """
     refine_plan for a fleet: every planner gets exactly what its own refine_plan(max_rounds, goal_tries) gives it -- node_seq, x_seq,
@@ -1129,60 +1173,36 @@ def refine_plans(planners, max_rounds=8, goal_tries=8):
     planners = list(planners)
     if not planners:
         return []
-    if len(set(id(p) for p in planners)) != len(planners):
-        raise ValueError("refine_plans: a planner appears twice.")
     if int(max_rounds) < 0 or int(goal_tries) < 1:
         raise ValueError("max_rounds must be >= 0 and goal_tries >= 1.")
-    for p in planners:
-        if not isinstance(p, Planner):
-            raise ValueError("refine_plans: expected Planner objects.")
-        if p.callback_mode:                                         # (as the last set_system left it, as in refine_plan)
-            raise ValueError("refine_plans: planners whose plugins are Python callables cannot be refined (the device cannot call them).")
-    runs = []
-    for p in planners:
-        try:
-            runs.append(p._refine_begin())
-        except RuntimeError as ex:
-            raise ValueError(str(ex).replace("refine_plan:", "refine_plans:"))
-    groups = {}
-    for k, (p, run) in enumerate(zip(planners, runs)):
-        if run is not None:
-            groups.setdefault((p.device, type(p.system)), []).append(k)
+    _fleet_check("refine_plans", planners, goal_tries)
+    runs = _fleet_begin("refine_plans", planners, lambda p: p._refine_begin())
     error = None
-    for g in sorted(groups, key=lambda g: groups[g][0]):
-        for first in range(0, len(groups[g]), 128):                 # (a native call takes at most 128 engines)
-            active = groups[g][first:first + 128]
-            try:
-                while True:
-                    active = [k for k in active if runs[k].rounds < int(max_rounds)]
-                    if not active:
-                        break
-                    wins = Engine.refine_round_multi([planners[k]._engine for k in active], [runs[k].core for k in active],
-                                                     [runs[k].H for k in active], [planners[k]._refine_incumbent(runs[k]) for k in active],
-                                                     goal_tries)
-                    winners = [(k, w) for k, w in zip(active, wins) if w is not None]
-                    if not winners:
-                        break
-                    failed = None
-                    try:
-                        new = Engine.refine_commit_multi([planners[k]._engine for k, _ in winners], [runs[k].core for k, _ in winners],
-                                                         [runs[k].H for k, _ in winners], [(w[1], w[2]) for _, w in winners], goal_tries)
-                    except nat.NativeError as ex:
-                        if getattr(ex, "results", None) is None:
-                            raise
-                        new, failed = ex.results, ex                # the other engines of the call did commit: their plans follow
-                    active = []
-                    for (k, w), ids in zip(winners, new):
-                        if ids is None:                             # capacity (or a failed chain): this planner stops with what it has
-                            continue
-                        planners[k]._refine_accept(runs[k], w[0], w[1], ids)
-                        active.append(k)
-                    if failed is not None:
-                        raise failed
-            except (nat.NativeError, ValueError) as ex:
-                error = ex                                          # raised below, once the rounds already accepted are adopted
-                break
-        if error is not None:
+    for active in _fleet_groups(planners, runs):
+        try:
+            while True:
+                active = [k for k in active if runs[k].rounds < int(max_rounds)]
+                if not active:
+                    break
+                wins = Engine.refine_round_multi([planners[k]._engine for k in active], [runs[k].core for k in active],
+                                                 [runs[k].H for k in active], [planners[k]._refine_incumbent(runs[k]) for k in active],
+                                                 goal_tries)
+                winners = [(k, w) for k, w in zip(active, wins) if w is not None]
+                if not winners:
+                    break
+                new, failed = _fleet_commit(lambda: Engine.refine_commit_multi(
+                    [planners[k]._engine for k, _ in winners], [runs[k].core for k, _ in winners], [runs[k].H for k, _ in winners],
+                    [(w[1], w[2]) for _, w in winners], goal_tries))
+                active = []
+                for (k, w), ids in zip(winners, new):
+                    if ids is None:                                 # capacity (or a failed chain): this planner stops with what it has
+                        continue
+                    planners[k]._refine_accept(runs[k], w[0], w[1], ids)
+                    active.append(k)
+                if failed is not None:
+                    raise failed
+        except (nat.NativeError, ValueError) as ex:
+            error = ex                                              # raised below, once the rounds already accepted are adopted
             break
     results = [0 if run is None else p._refine_end(run) for p, run in zip(planners, runs)]
     if error is not None:
@@ -1207,25 +1227,10 @@ def connect_vias(planners, waypoints, goal_tries=8, nodes=None, finish_on_goal=N
     wrong length, an array not of shape (Q, nstates).  If a native call fails, the planners that did commit adopt their plans -- those
     of the failing commit call included -- then the error is raised.
     """
-    planners = list(planners)
-    if int(goal_tries) < 1:
-        raise ValueError("goal_tries must be >= 1.")
-    waypoints = list(waypoints)
+    planners, waypoints, nodes = list(planners), list(waypoints), None if nodes is None else list(nodes)
     if len(waypoints) != len(planners):
         raise ValueError("connect_vias: expected one waypoint array (or None) per planner.")
-    if nodes is not None:
-        nodes = list(nodes)
-        if len(nodes) != len(planners):
-            raise ValueError("connect_vias: expected one id list (or None) per planner.")
-    if not planners:
-        return []
-    if len(set(id(p) for p in planners)) != len(planners):
-        raise ValueError("connect_vias: a planner appears twice.")
-    for p in planners:
-        if not isinstance(p, Planner):
-            raise ValueError("connect_vias: expected Planner objects.")
-        if p.callback_mode:                                         # (as the last set_system left it, as in connect_via)
-            raise ValueError("connect_vias: planners whose plugins are Python callables cannot be searched (the device cannot call them).")
+    _fleet_check("connect_vias", planners, goal_tries, nodes)
     ways = []
     for k, (p, w) in enumerate(zip(planners, waypoints)):
         way = np.ascontiguousarray(() if w is None else w, dtype=np.float64)
@@ -1234,41 +1239,25 @@ def connect_vias(planners, waypoints, goal_tries=8, nodes=None, finish_on_goal=N
         if way.ndim != 2 or way.shape[1] != p.nstates:
             raise ValueError("connect_vias: expected waypoints of shape (Q, %d) for planner %d." % (p.nstates, k))
         ways.append(way)
-    runs = []
-    for p in planners:
-        try:
-            runs.append(p._connect_begin())
-        except RuntimeError as ex:
-            raise ValueError(str(ex).replace("refine_plan:", "connect_vias:").replace("connect_goal:", "connect_vias:"))
+    runs = _fleet_begin("connect_vias", planners, lambda p: p._connect_begin())
     results = [False] * len(planners)
-    groups = {}
-    for k, (p, run) in enumerate(zip(planners, runs)):
-        if run is not None:
-            groups.setdefault((p.device, type(p.system)), []).append(k)
-    for g in sorted(groups, key=lambda g: groups[g][0]):
-        for first in range(0, len(groups[g]), 128):                 # (a native call takes at most 128 engines)
-            mine = groups[g][first:first + 128]
-            wins = Engine.connect_via_search_multi([planners[k]._engine for k in mine], [ways[k] for k in mine], [runs[k].H for k in mine],
-                                                   [planners[k]._connect_incumbent(runs[k]) for k in mine], goal_tries,
-                                                   None if nodes is None else [nodes[k] for k in mine])
-            winners = [(k, w) for k, w in zip(mine, wins) if w is not None]
-            if not winners:
+    for mine in _fleet_groups(planners, runs):
+        wins = Engine.connect_via_search_multi([planners[k]._engine for k in mine], [ways[k] for k in mine], [runs[k].H for k in mine],
+                                               [planners[k]._connect_incumbent(runs[k]) for k in mine], goal_tries,
+                                               None if nodes is None else [nodes[k] for k in mine])
+        winners = [(k, w) for k, w in zip(mine, wins) if w is not None]
+        if not winners:
+            continue
+        new, failed = _fleet_commit(lambda: Engine.connect_via_commit_multi(
+            [planners[k]._engine for k, _ in winners], [(w[1], w[2]) for _, w in winners], [ways[k] for k, _ in winners],
+            [runs[k].H for k, _ in winners], goal_tries))
+        for (k, w), ids in zip(winners, new):
+            if ids is None:                                         # capacity (or a failed chain): this planner keeps what it has
                 continue
-            failed = None
-            try:
-                new = Engine.connect_via_commit_multi([planners[k]._engine for k, _ in winners], [(w[1], w[2]) for _, w in winners],
-                                                      [ways[k] for k, _ in winners], [runs[k].H for k, _ in winners], goal_tries)
-            except nat.NativeError as ex:
-                if getattr(ex, "results", None) is None:
-                    raise
-                new, failed = ex.results, ex                        # the other engines of the call did commit: their plans follow
-            for (k, w), ids in zip(winners, new):
-                if ids is None:                                     # capacity (or a failed chain): this planner keeps what it has
-                    continue
-                planners[k]._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
-                results[k] = True
-            if failed is not None:
-                raise failed
+            planners[k]._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
+            results[k] = True
+        if failed is not None:
+            raise failed
     return results
 
 
@@ -1288,55 +1277,24 @@ def connect_goals(planners, goal_tries=8, nodes=None, finish_on_goal=None):
     `nodes` sequence of the wrong length.  If a native call fails, the planners that did commit adopt their plans -- those of the
     failing commit call included -- then the error is raised.
     """
-    planners = list(planners)
-    if int(goal_tries) < 1:
-        raise ValueError("goal_tries must be >= 1.")
-    if nodes is not None:
-        nodes = list(nodes)
-        if len(nodes) != len(planners):
-            raise ValueError("connect_goals: expected one id list (or None) per planner.")
-    if not planners:
-        return []
-    if len(set(id(p) for p in planners)) != len(planners):
-        raise ValueError("connect_goals: a planner appears twice.")
-    for p in planners:
-        if not isinstance(p, Planner):
-            raise ValueError("connect_goals: expected Planner objects.")
-        if p.callback_mode:                                         # (as the last set_system left it, as in connect_goal)
-            raise ValueError("connect_goals: planners whose plugins are Python callables cannot be searched (the device cannot call them).")
-    runs = []
-    for p in planners:
-        try:
-            runs.append(p._connect_begin())
-        except RuntimeError as ex:
-            raise ValueError(str(ex).replace("refine_plan:", "connect_goals:").replace("connect_goal:", "connect_goals:"))
+    planners, nodes = list(planners), None if nodes is None else list(nodes)
+    _fleet_check("connect_goals", planners, goal_tries, nodes)
+    runs = _fleet_begin("connect_goals", planners, lambda p: p._connect_begin())
     results = [False] * len(planners)
-    groups = {}
-    for k, (p, run) in enumerate(zip(planners, runs)):
-        if run is not None:
-            groups.setdefault((p.device, type(p.system)), []).append(k)
-    for g in sorted(groups, key=lambda g: groups[g][0]):
-        for first in range(0, len(groups[g]), 128):                 # (a native call takes at most 128 engines)
-            mine = groups[g][first:first + 128]
-            wins = Engine.connect_search_multi([planners[k]._engine for k in mine], [runs[k].H for k in mine],
-                                               [planners[k]._connect_incumbent(runs[k]) for k in mine], goal_tries,
-                                               None if nodes is None else [nodes[k] for k in mine])
-            winners = [(k, w) for k, w in zip(mine, wins) if w is not None]
-            if not winners:
+    for mine in _fleet_groups(planners, runs):
+        wins = Engine.connect_search_multi([planners[k]._engine for k in mine], [runs[k].H for k in mine],
+                                           [planners[k]._connect_incumbent(runs[k]) for k in mine], goal_tries,
+                                           None if nodes is None else [nodes[k] for k in mine])
+        winners = [(k, w) for k, w in zip(mine, wins) if w is not None]
+        if not winners:
+            continue
+        new, failed = _fleet_commit(lambda: Engine.connect_commit_multi(
+            [planners[k]._engine for k, _ in winners], [w[1] for _, w in winners], [runs[k].H for k, _ in winners], goal_tries))
+        for (k, w), ids in zip(winners, new):
+            if ids is None:                                         # capacity (or a failed chain): this planner keeps what it has
                 continue
-            failed = None
-            try:
-                new = Engine.connect_commit_multi([planners[k]._engine for k, _ in winners], [w[1] for _, w in winners],
-                                                  [runs[k].H for k, _ in winners], goal_tries)
-            except nat.NativeError as ex:
-                if getattr(ex, "results", None) is None:
-                    raise
-                new, failed = ex.results, ex                        # the other engines of the call did commit: their plans follow
-            for (k, w), ids in zip(winners, new):
-                if ids is None:                                     # capacity (or a failed chain): this planner keeps what it has
-                    continue
-                planners[k]._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
-                results[k] = True
-            if failed is not None:
-                raise failed
+            planners[k]._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
+            results[k] = True
+        if failed is not None:
+            raise failed
     return results

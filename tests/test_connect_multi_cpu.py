@@ -122,13 +122,23 @@ def test_multi_search_keeps_its_solo_twins_frame_and_occupancy():
 def test_fleet_connection_stays_plain_launches():
     """One stream, plain launches: no cooperative launch, no grid-wide barrier; the multi kernel wraps the shared body, it holds no
     copy of the chain."""
-    for f in ("connect.hpp", "engine_connect.hpp"):
-        text = open(os.path.join(ROOT, "lqrrt_amd", "csrc", f)).read()
+    csrc = os.path.join(ROOT, "lqrrt_amd", "csrc")
+    for f in ("connect.hpp", "engine_connect.hpp", "engine_refine.hpp"):        # (engine_refine.hpp: the multi path the calls run on)
+        text = open(os.path.join(csrc, f)).read()
         for word in ("hipLaunchCooperativeKernel", "hipModuleLaunchCooperativeKernel", "cooperative_groups", "grid.sync", "this_grid"):
             assert word not in text, (f, word)
-    src = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "connect.hpp")).read()
+    src = open(os.path.join(csrc, "connect.hpp")).read()
     assert "k_connect_search_multi" in src and "multi_engine_of" in src and "struct ConnectDesc" in src
     assert "S::step(" not in src and src.count("refine_edge<S>(") == 1 and src.count("connect_search_body<S>(") == 2
-    host = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine_connect.hpp")).read()
+    # the depth pass: defined once in all of csrc, and every tree-wide search reaches it -- connect's and reach's solo search, via's,
+    # and the two searches for several trees
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))}
+    assert sum(t.count("static int connect_depths(") for t in texts.values()) == 1
+    host = texts["engine_connect.hpp"]
     assert host.count("connect_depths(") == 3                       # the depth pass: one definition, the solo and the multi search
+    assert "static int connect_depths(" in host and host.count("TRY(connect_depths(") == 2
+    for f in ("engine_reach.hpp", "engine_connect_via.hpp", "engine_connect_via_multi.hpp"):
+        assert texts[f].count("TRY(connect_depths(") == 1, f
+    # the batched commit has no kernel and no runner of its own: it is the refinement's
     assert "refine_multi_scratch(" in host and "refine_commit_multi_run(" in host and "k_refine_commit_multi" not in host
+    assert host.count("hipLaunchKernelGGL(") == 3                   # the solo search, the shared solo commit, the multi search

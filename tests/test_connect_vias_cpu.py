@@ -168,7 +168,7 @@ def test_connect_vias_shares_the_connection_steps_and_calls_the_batched_pair():
 
 
 def test_fleet_via_stays_plain_launches_that_wrap_the_solo_bodies():
-    for f in ("connect_via_multi.hpp", "engine_connect_via_multi.hpp"):
+    for f in ("connect_via_multi.hpp", "engine_connect_via_multi.hpp", "engine_connect_via.hpp", "engine_connect.hpp", "engine_refine.hpp"):
         text = open(os.path.join(ROOT, "lqrrt_amd", "csrc", f)).read()
         for word in ("hipLaunchCooperativeKernel", "hipModuleLaunchCooperativeKernel", "cooperative_groups", "grid.sync", "this_grid"):
             assert word not in text, (f, word)
@@ -182,10 +182,24 @@ def test_fleet_via_stays_plain_launches_that_wrap_the_solo_bodies():
     engine = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine.hip")).read()
     assert engine.index('#include "engine_connect_via.hpp"') < engine.index('#include "engine_connect_via_multi.hpp"')
     host = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine_connect_via_multi.hpp")).read()
-    for name in ("connect_multi_check(", "connect_via_check(", "connect_depths(", "connect_depth_of(", "range_ok(", "refine_multi_scratch(",
-                 "multi_sync_proto(", "retain_grid(", "refine_multi_fail(", "refine_adopt("):
+    # the shared checks, depth functions, scratch, proto sync, grid and adopt rather than copies: connect_via_winner_check stands for
+    # range_ok and connect_depth_of, refine_multi_protos for multi_sync_proto, multi_grid for retain_grid, multi_commit_adopt for
+    # refine_adopt; a failed call drains the stream (StreamDrain, armed before every upload)
+    for name in ("connect_multi_check(", "connect_via_check(", "connect_depths(", "connect_via_winner_check(", "connect_via_candidates_check(",
+                 "connect_via_deepest_check(", "incumbent_check(", "multi_id_list(", "multi_chunks(", "multi_commit_head(",
+                 "refine_multi_scratch(", "refine_multi_protos(", "multi_grid(", "multi_search_keys(", "multi_commit_adopt(",
+                 "StreamDrain drain(st)", "connect_via_fill_args(", "connect_via_decode("):
         assert name in host, name
+    assert host.count("StreamDrain drain(st)") == 2 and host.count("drain.arm();") == 2     # the search and the commit
     assert "dalloc(" not in host and "hipMalloc" not in host       # no buffer of its own
+    for copied in ("range_ok(", "connect_depth_of(", "multi_sync_proto(", "retain_grid(", "refine_adopt(", "0x7fffffff", "0xffffffff", "g_err"):
+        assert copied not in host, copied
+    shared = {"engine_connect_via.hpp": ("range_ok(", "connect_winner_check("), "engine_connect.hpp": ("connect_depth_of(", "range_ok("),
+              "engine_refine.hpp": ("multi_sync_proto(", "retain_grid(", "refine_adopt(", "struct StreamDrain", "g_err = keep;")}
+    for f, names in shared.items():
+        text = open(os.path.join(ROOT, "lqrrt_amd", "csrc", f)).read()
+        for name in names:
+            assert name in text, (f, name)
 
 
 def test_abi_declares_the_two_calls_and_keeps_its_version():
