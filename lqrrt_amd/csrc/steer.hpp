@@ -69,6 +69,18 @@ struct SteerFuse {
 //     in k_steer); LQRRT_DARE_WAVEFRONTS=1 keeps round 3's one wavefront per rollout.
 template <class S, class = void> struct wants_two : std::false_type {};
 template <class S> struct wants_two<S, std::enable_if_t<S::TWO_WAVEFRONTS>> : std::true_type {};
+// Systems that spell the chain wavefront's torque and finish step for a wavefront that holds one rollout declare S::CHAIN_STEP:
+// S::chain_torque (a scalar branch where duo_chain has exec-mask regions) and S::chain_finish, which works on the per-lane row
+// coefficients that S::chain_rows loads once per rollout (systems.hpp, "LANE ROWS").
+struct NoChainRows {};
+template <class S, class = void> struct chain_step : std::false_type {
+    using Rows = NoChainRows;
+    __device__ __forceinline__ static Rows rows(const double*, int) { return {}; }
+};
+template <class S> struct chain_step<S, std::enable_if_t<S::CHAIN_STEP>> : std::true_type {
+    using Rows = typename S::ChainRows;
+    __device__ __forceinline__ static Rows rows(const double* P, int lane) { return S::chain_rows(P, lane); }
+};
 template <class S> constexpr int steer_wavefronts_max() { return has_dare_gain<S>::value ? 4 : is_packed<S>::value ? 3 : wants_two<S>::value ? 2 : 1; }
 struct DuoLds {
     double pk[2 * MAXN + 4 + MAXM];      // two wavefronts (boats): xn | trn | e | u   of the newest step
@@ -189,7 +201,8 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
     //   heading (1): cos/sin of heading p+1 (h + vh dt: two components of x_p) and the erf angle there -> tr / e2b[(p+1) & 1]
     //   checker (2): the sequential loop's tests on step p-1 (feasibility of x_p, error growth, convergence, horizon), history
     //                entry or `stop`, read by everybody behind B_p+1.  The chain runs one step ahead of the verdict; the step it
-    //                computes while the last verdict is made is thrown away (the node comes from the history).
+    //                computes while the last verdict is made is thrown away (the node comes from the history) -- except at the
+    //                horizon, which the chain sees coming: it computes no step p > H.
     constexpr bool CH = NWF == 3 && is_packed<S>::value;
     if constexpr (CH) {
         if (threadIdx.x >= 128) {
@@ -203,6 +216,11 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             double tolr[S::N], last[S::N];
 #pragma unroll
             for (int d = 0; d < S::N; ++d) { tolr[d] = tol_l[d]; last[d] = INFINITY; }           // planner.py:377
+            // the model constants the tests read (a speed box) in registers, like the chain's: from LDS each bound is a dependent
+            // round trip in front of the sweep, one per early return of S::feasible
+            double Pc[S::NP];
+#pragma unroll
+            for (int i = 0; i < S::NP; ++i) Pc[i] = Pl[i];
             int cnt = 0, steps = 0;
             bool stopped = false;
             for (int p = 1;; ++p) {
@@ -217,7 +235,7 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
                 for (int j = 0; j < S::M; ++j) u[j] = pk[2 * S::N + j];
                 trn[0] = duo.tr[p & 1][0]; trn[1] = duo.tr[p & 1][1];
                 bool rec_now = false;
-                stopped = rollout_check<S>(Pl, g, gl, r, xn, trn, e, u, lane, cnt, steps, last, tolr, hx, hu, htr, duo, &rec_now);
+                stopped = rollout_check<S>(Pc, g, gl, r, xn, trn, e, u, lane, cnt, steps, last, tolr, hx, hu, htr, duo, &rec_now);
                 if (rec_now) { rollout_record<S>(xn, trn, u, cnt, hx, hu, htr); ++cnt; }
                 STEP_TS(cs1);
                 STEP_ACC(5, cs0, cs1);
@@ -676,24 +694,34 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         double Pc[S::NP];
 #pragma unroll
         for (int i = 0; i < S::NP; ++i) Pc[i] = Pl[i];
+        [[maybe_unused]] const typename chain_step<S>::Rows rows = chain_step<S>::rows(Pl, lane);     // (per-lane addresses: from LDS)
         for (int p = 0;; ++p) {
             STEP_TS(ms0);
-            double e[S::N], u[S::M], xn[S::N];
-            if (p >= 1) {
-                trig[0] = duo.tr[p & 1][0]; trig[1] = duo.tr[p & 1][1];
-                const double e2 = duo.e2b[p & 1];
-                S::gain(Pc, x, trig, x, K);                                       // planner.py:436: K = lqr(x_p)
-                S::quad_effort(xt, x, K, e2, e, u);                               // planner.py:386-387
-            } else {
-                S::trio_effort(xt, ttrig, x, trig, K, e, u);                      // (the parent's own gain)
+            // Step p > H has no reader: the checker ends the edge in period H + 1 whatever it finds there (infeasible, or
+            // steps = H + 1 > H), so that period's chain iteration goes straight to its barrier.
+            if (p <= r.H) {
+                double e[S::N], u[S::M], xn[S::N];
+                if (p >= 1) {
+                    trig[0] = duo.tr[p & 1][0]; trig[1] = duo.tr[p & 1][1];
+                    const double e2 = duo.e2b[p & 1];
+                    S::gain(Pc, x, trig, x, K);                                   // planner.py:436: K = lqr(x_p)
+                    S::quad_effort(xt, x, K, e2, e, u);                           // planner.py:386-387
+                } else {
+                    S::trio_effort(xt, ttrig, x, trig, K, e, u);                  // (the parent's own gain)
+                }
+                if constexpr (chain_step<S>::value) {
+                    const double rud = S::chain_torque(Pc, x, trig);
+                    S::chain_finish(Pc, rows, lane, x, trig, u, rud, r.dt, xn);   // planner.py:390
+                } else {
+                    const double rud = S::duo_chain(Pc, x, trig);
+                    S::duo_finish(Pc, x, trig, u, rud, r.dt, xn);                 // planner.py:390
+                }
+                double* pk = duo.pk2[(p + 1) & 1];
+#pragma unroll
+                for (int d = 0; d < S::N; ++d) { pk[d] = xn[d]; pk[S::N + d] = e[d]; x[d] = xn[d]; }
+#pragma unroll
+                for (int j = 0; j < S::M; ++j) pk[2 * S::N + j] = u[j];
             }
-            const double rud = S::duo_chain(Pc, x, trig);
-            S::duo_finish(Pc, x, trig, u, rud, r.dt, xn);                         // planner.py:390
-            double* pk = duo.pk2[(p + 1) & 1];
-#pragma unroll
-            for (int d = 0; d < S::N; ++d) { pk[d] = xn[d]; pk[S::N + d] = e[d]; x[d] = xn[d]; }
-#pragma unroll
-            for (int j = 0; j < S::M; ++j) pk[2 * S::N + j] = u[j];
             STEP_TS(ms1);
             __syncthreads();                                         // B_p+1: x_p+1 and the verdict on x_p are there
             STEP_TS(ms4);

@@ -221,38 +221,54 @@ __device__ __forceinline__ bool grid_hits(const Geo& g, const GeoL& gl, double p
     return __any(hit) != 0;
 }
 
+// Value held by lane j of the wavefront (j wave-uniform), for every lane: two v_readlane, no LDS round trip.
+__device__ __forceinline__ double lane_read(double v, int j) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
+    return __hiloint2double(hi, lo);
+}
+
+// The sweep proper works on registers: lane v of a tile of 64 holds hull point v, rotated ONCE for all the near obstacles of the
+// cull tile (it does not depend on the obstacle), and an obstacle's centre and threshold come from the lane that culled it.
+// Every hull point is a 50-cycle LDS round trip away on a wavefront that does nothing else meanwhile; before, each near
+// obstacle paid it again, with the rotation.  The same operations on the same operands: answers are exact as before.
 __device__ __forceinline__ bool hull_hits(const GeoL& g, double px, double py, double c, double s,
                                           bool extra2p, int lane) {
     ABL_IF_NOFEAS(return false;)
     bool hit = false;
     const double ms = -s;
+    // (stage_geo put the hull points into LDS for every caller of this sweep -- only the occupancy-grid model may leave them
+    //  in HBM -- but GeoL cannot say so: name the address space, or each read is a flat load that waits on both counters)
+    const __attribute__((address_space(3))) double* vps = (const __attribute__((address_space(3))) double*)g.vps;
     for (int o0 = 0; o0 < g.O; o0 += 64) {
         const int o = o0 + lane;
         bool near = false;
+        double ox = 0.0, oy = 0.0, thr = 0.0;
         if (o < g.O) {
             // cull: an obstacle can only contain a hull point if its centre, seen from the vehicle's frame, lies within the
             // hull's bounding box grown by the (padded) radius -- much tighter than a bounding circle for a 2:1 hull, and
             // conservative (padding 1e-9 >> the rounding of these few operations), so the exact tests below decide as before
-            const double ox = g.oc[4 * o], oy = g.oc[4 * o + 1], rp = g.oc[4 * o + 3];
+            ox = g.oc[4 * o]; oy = g.oc[4 * o + 1]; thr = g.oc[4 * o + 2];
+            const double rp = g.oc[4 * o + 3];
             const double dx = ox - px, dy = oy - py;
             const double cbx = c * dx + s * dy, cby = c * dy + ms * dx;
             near = (cbx >= g.bb[0] - rp) && (cbx <= g.bb[1] + rp) && (cby >= g.bb[2] - rp) && (cby <= g.bb[3] + rp);
             if (extra2p) {
                 const double ex = (px + px) - ox, ey = (py + py) - oy;
-                hit |= (ex * ex + ey * ey) <= g.oc[4 * o + 2];
+                hit |= (ex * ex + ey * ey) <= thr;
             }
         }
-        unsigned long long m = __ballot(near);
-        while (m) {
-            const int j = __builtin_ctzll(m);
-            m &= m - 1;
-            const double ox = g.oc[4 * (o0 + j)], oy = g.oc[4 * (o0 + j) + 1], thr = g.oc[4 * (o0 + j) + 2];
-            for (int v = lane; v < g.V; v += 64) {
-                const double bx = g.vps[v], by = g.vps[g.V + v];
-                const double vx = px + (c * bx + ms * by);
-                const double vy = py + (s * bx + c * by);
-                const double dx = vx - ox, dy = vy - oy;
-                hit |= (dx * dx + dy * dy) <= thr;
+        const unsigned long long m = __ballot(near);
+        if (m == 0) continue;
+        for (int v0 = 0; v0 < g.V; v0 += 64) {
+            const bool live = v0 + lane < g.V;
+            const int v = live ? v0 + lane : 0;                  // (a lane past the hull computes on point 0 and does not vote)
+            const double bx = vps[v], by = vps[g.V + v];
+            const double vx = px + (c * bx + ms * by);
+            const double vy = py + (s * bx + c * by);
+            for (unsigned long long mm = m; mm; mm &= mm - 1) {
+                const int j = __builtin_ctzll(mm);
+                const double dx = vx - lane_read(ox, j), dy = vy - lane_read(oy, j);
+                hit |= live && (dx * dx + dy * dy) <= lane_read(thr, j);
             }
         }
     }
@@ -301,6 +317,14 @@ struct BoatCommon {
     __device__ __forceinline__ static double rudder_term(double gainv, double vmin2, const double* x, double c, double s) {
         ABL_IF_NORUDDER(return 0.0;)
         if (torque_direct(vmin2, x)) return gainv * lq_atan2(x[4], x[3]);
+        return rudder_ref(gainv, x, c, s);
+    }
+    // The same on a wavefront whose lanes all hold ONE rollout (k_steer's chain rollout).  The compiler cannot know that the choice
+    // of arm is wave-uniform and would predicate both arms with the exec mask, the reference's 600-instruction sequence inside the
+    // step's straight line; read from one lane the choice is a scalar branch, and that sequence lies outside the step.
+    __device__ __forceinline__ static double rudder_term_uniform(double gainv, double vmin2, const double* x, double c, double s) {
+        ABL_IF_NORUDDER(return 0.0;)
+        if (__builtin_amdgcn_readfirstlane((int)torque_direct(vmin2, x))) return gainv * lq_atan2(x[4], x[3]);
         return rudder_ref(gainv, x, c, s);
     }
 
@@ -441,6 +465,14 @@ struct BoatCommon {
         else if (x[3] < 0.0) xn[5] = clipd(fabs(xn[3] / vneg0), 0.0, 1.0) * xn[5];
         if (xn[3] < 0.0) xn[3] = 0.0;
     }
+    // carlike() without its two predicated arms: ONE division by the selected speed limit, kept by a select.  A boat with x[3] = 0
+    // (or NaN) divides too and drops the quotient; every other boat performs carlike()'s operations on carlike()'s operands.
+    __device__ __forceinline__ static void carlike_straight(const double* x, double vpos0, double vneg0, double* xn) {
+        const bool pos = x[3] > 0.0, neg = x[3] < 0.0;
+        const double scaled = clipd(fabs(xn[3] / (pos ? vpos0 : vneg0)), 0.0, 1.0) * xn[5];
+        xn[5] = (pos || neg) ? scaled : xn[5];
+        if (xn[3] < 0.0) xn[3] = 0.0;
+    }
 };
 
 struct BoatAdvanced : BoatCommon {
@@ -474,6 +506,53 @@ struct BoatAdvanced : BoatCommon {
     __device__ __forceinline__ static void duo_finish(const double* P, const double* x, const double* trig, const double* u, double rud, double dt, double* xn) {
         double uc[3] = {u[0], u[1], u[2] + rud};
         thrust_and_integrate(P, x, trig, uc, dt, xn);
+    }
+    // The chain rollout's own spelling of the two pieces above (k_steer takes them where a system has them).  Its wavefront holds
+    // one rollout in all lanes, so the step's data-dependent choices are scalar branches or selects, never exec-mask regions.
+    static constexpr bool CHAIN_STEP = true;
+    __device__ __forceinline__ static double chain_torque(const double* P, const double* x, const double* trig) {
+        return rudder_term_uniform(P[37], P[52], x, trig[0], trig[1]);
+    }
+    // The finish step in LANE ROWS.  thrust_and_integrate is scalar arithmetic that all 64 lanes repeat: four thruster rows
+    // invB u with a clip each, three rows B t, three drag terms, three velocity updates -- rows that do not depend on one another.
+    // Here lane q of every quad holds row q (lane 3 repeats row 2 where there are three): its coefficients are loaded once per
+    // rollout by per-lane address (chain_rows), ONE multiply-add sequence serves all rows, and what the next stage needs in every
+    // lane goes round the quad with DPP moves (quad_bcast: the four thrusts, the three new velocities = 14 moves for ~60
+    // instructions of rows).  A lane's arithmetic for its row is thrust_and_integrate's for that row, operand for operand.
+    struct ChainRows { double ib0, ib1, ib2, tlo, thi, b0, b1, b2, b3, invM, Dpos, Dneg; };
+    __device__ __forceinline__ static ChainRows chain_rows(const double* P, int lane) {
+        const int q = lane & 3, i = q < 3 ? q : 2;
+        ChainRows w;
+        w.ib0 = P[21 + 3 * q]; w.ib1 = P[21 + 3 * q + 1]; w.ib2 = P[21 + 3 * q + 2];
+        w.thi = P[33 + q]; w.tlo = -P[33 + q];
+        w.b0 = P[9 + 4 * i]; w.b1 = P[9 + 4 * i + 1]; w.b2 = P[9 + 4 * i + 2]; w.b3 = P[9 + 4 * i + 3];
+        w.invM = P[i]; w.Dpos = P[3 + i]; w.Dneg = P[6 + i];
+        return w;
+    }
+    __device__ __forceinline__ static void chain_finish(const double* P, const ChainRows& w, int lane, const double* x, const double* trig,
+                                                        const double* u, double rud, double dt, double* xn) {
+        const double c = trig[0], s = trig[1];
+        const double u2 = u[2] + rud;
+        double a = w.ib0 * u[0];                                 // thruster q: clip(invB[q] . u)
+        a += w.ib1 * u[1];
+        a += w.ib2 * u2;
+        const double tq = clipd(a, w.tlo, w.thi);
+        const double t0 = quad_bcast<0>(tq), t1 = quad_bcast<1>(tq), t2 = quad_bcast<2>(tq), t3 = quad_bcast<3>(tq);
+        double us = w.b0 * t0;                                   // force row i: B[i] . t
+        us += w.b1 * t1;
+        us += w.b2 * t2;
+        us += w.b3 * t3;
+        const int q = lane & 3;
+        const double x3 = x[3], x4 = x[4], x5 = x[5];            // (values, not a choice of addresses: that would put x into scratch)
+        const double v = q == 0 ? x3 : q == 1 ? x4 : x5;         // euler(): row 3 + i
+        const double D = (v >= 0.0) ? w.Dpos : w.Dneg;
+        const double vdot = w.invM * (us - D * v);
+        const double vn = v + vdot * dt;
+        xn[0] = x[0] + (c * x[3] + (-s) * x[4]) * dt;
+        xn[1] = x[1] + (s * x[3] + c * x[4]) * dt;
+        xn[2] = x[2] + x[5] * dt;
+        xn[3] = quad_bcast<0>(vn); xn[4] = quad_bcast<1>(vn); xn[5] = quad_bcast<2>(vn);
+        carlike_straight(x, P[38], P[39], xn);
     }
     __device__ __forceinline__ static void thrust_and_integrate(const double* P, const double* x, const double* trig, double* u, double dt, double* xn) {
         const double c = trig[0], s = trig[1];
