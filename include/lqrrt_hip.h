@@ -575,6 +575,35 @@ int lqrrt_connect_via_commit_multi(lqrrt_engine** engines, int n, const int32_t*
                                    const int32_t* horizon_iters, int32_t* const* ids_out, const int32_t* cap_ids,
                                    int32_t* counts_out, void* stream);
 
+/* lqrrt_reach_search / lqrrt_reach_commit for n engines at once (fleet_goal_costs / retargets: the task-assignment matrix of a fleet,
+ * P trees x T targets), with the conventions of lqrrt_connect_search_multi: 1 <= n <= 128 distinct engines of one device and one
+ * compiled-in model, cut into chunks of up to 32 engines that take part and fewer than 2^32 threads per launch; per chunk one image
+ * in a scratch of its first engine (not part of lqrrt_engine_footprint), one copy up, one launch, one copy back; one synchronise
+ * per call.  Every argument of every engine and target is checked, with the rules of the one-engine calls (messages name the
+ * engine), before anything is written or launched.
+ *
+ * lqrrt_reach_search_multi: engine k is asked about its own T[k] targets (1 to 1024) -- goals[k], lo[k], hi[k]: host arrays
+ * [T[k]][n_states] as lqrrt_reach_search takes them; nodes / counts: lqrrt_connect_search_multi's id lists (nodes NULL or nodes[k]
+ * NULL: every node of tree k; counts[k] = 0: no launch share, no winner); goal_tries and horizon_iters [n]; incumbents NULL, or n
+ * pointers each NULL (2^31-1 for every target) or [T[k]].  cost_out[k] and node_out[k] point to [T[k]]: per target the result of
+ * lqrrt_reach_search.  Engine k occupies T[k] * count_k workgroups of its chunk's launch, target-major; every (engine, target) pair
+ * has a best key of its own, so each winner is the one the engine's own lqrrt_reach_search finds. */
+int lqrrt_reach_search_multi(lqrrt_engine** engines, int n, const double* const* goals, const double* const* lo,
+                             const double* const* hi, const int32_t* T, const int32_t* const* nodes, const int32_t* counts,
+                             const int32_t* goal_tries, const int32_t* horizon_iters, const int64_t* const* incumbents,
+                             int64_t* const* cost_out, int32_t* const* node_out, void* stream);
+
+/* lqrrt_reach_commit_multi: one commit launch per chunk, one workgroup per engine with a winner nodes[k] toward its ONE target
+ * goal[k], lo[k], hi[k] ([n_states] each); ids_out[k] [cap_ids[k] >= goal_tries[k]] receives the new ids and counts_out[k] their
+ * number -- 0 for nodes[k] = -1 (that engine's other arguments but goal_tries and horizon_iters are not read),
+ * LQRRT_E_CAPACITY when that tree cannot hold the chain, LQRRT_E_STATE when the chain does not end in the target's box: that
+ * engine's tree and host mirrors are then unchanged, the others commit, and the call returns 0.  The engines' own goals and boxes
+ * are neither read nor written. */
+int lqrrt_reach_commit_multi(lqrrt_engine** engines, int n, const double* const* goal, const double* const* lo,
+                             const double* const* hi, const int32_t* nodes /* -1: no winner */, const int32_t* goal_tries,
+                             const int32_t* horizon_iters, int32_t* const* ids_out, const int32_t* cap_ids, int32_t* counts_out,
+                             void* stream);
+
 /* ---------------------------------------------------------------- wave engine -------- */
 
 /* Explicit sample stream: the caller supplies the samples (a user xrand_gen function,

@@ -12,13 +12,16 @@ lqrrt_amd -- MI355X-native expansion engine behind the jnez71/lqRRT Python API.
 Exports mirror lqrrt/__init__.py:1-2 of the reference (Constraints, Planner) plus Tree and
 the native problem plugins (systems), update_plans (several planners through shared native calls: one GPU, many
 trees -- planner.py), refine_plans (their found plans shortened through shared calls), connect_goals (the plans whose
-budget ran out before a goal hit connected to the goal through shared calls) and connect_vias (the same through each planner's own
-list of waypoints).  Importing works without a GPU; computing does not.
+budget ran out before a goal hit connected to the goal through shared calls), connect_vias (the same through each planner's own
+list of waypoints), fleet_goal_costs (what every planner's tree would pay to reach each of a shared list of places, one matrix
+through shared calls) and retargets (every planner given a new goal from the tree it holds, through shared calls).  Importing works
+without a GPU; computing does not.
 """
 from .constraints import Constraints
-from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias
+from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias, fleet_goal_costs, retargets
 from .tree import Tree
 from . import systems
 from . import dare
 
-__all__ = ["Constraints", "Planner", "Tree", "systems", "dare", "update_plans", "refine_plans", "connect_goals", "connect_vias"]
+__all__ = ["Constraints", "Planner", "Tree", "systems", "dare", "update_plans", "refine_plans", "connect_goals", "connect_vias",
+           "fleet_goal_costs", "retargets"]

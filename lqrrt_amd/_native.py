@@ -129,6 +129,8 @@ SIGNATURES = {
     "lqrrt_connect_commit_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_connect_via_search_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_connect_via_commit_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lqrrt_reach_search_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lqrrt_reach_commit_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_engine_push_samples": (_I, [_P, _P, _I]),
     "lqrrt_engine_queued_samples": (_I, [_P]),
     "lqrrt_record_layout": (_I, [_P, _P]),

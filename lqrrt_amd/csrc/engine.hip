@@ -88,6 +88,7 @@ static int fail(int code, const char* fmt, ...) {
 #include "engine_refine.hpp"      // ABI: refine_search / refine_commit (Planner.refine_plan; + _multi: retain_grid); the host path the next four share
 #include "engine_connect.hpp"     // ABI: connect_search / connect_commit (Planner.connect_goal: goal chains from every tree node; + _multi)
 #include "engine_reach.hpp"       // ABI: reach_search / reach_commit (Planner.goal_costs / retarget: one tree asked about many goals)
+#include "engine_reach_multi.hpp" // ABI: reach_search_multi / reach_commit_multi (fleet_goal_costs / retargets: the same for several trees)
 #include "engine_connect_via.hpp" // ABI: connect_via_search / connect_via_commit (Planner.connect_via: goal chains through waypoints)
 #include "engine_connect_via_multi.hpp" // ABI: connect_via_search_multi / connect_via_commit_multi (connect_vias: the same for several trees)
 

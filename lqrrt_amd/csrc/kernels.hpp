@@ -10,7 +10,8 @@
 //   k_refine_search / _commit (build-only: Planner.refine_plan, chains of k_steer's rollout over a found plan; refine.hpp)
 //   k_connect_search (+ _multi) (build-only: Planner.connect_goal / connect_goals, the same chains from every node of the tree to
 //                            the goal; connect.hpp)
-//   k_reach_search           (build-only: Planner.goal_costs / retarget, those chains to many goals per launch; reach.hpp)
+//   k_reach_search (+ _multi, k_reach_commit_multi) (build-only: Planner.goal_costs / retarget and fleet_goal_costs / retargets,
+//                            those chains to many goals per launch; reach.hpp, reach_multi.hpp)
 //   k_connect_via_search / _commit (+ _multi) (build-only: Planner.connect_via / connect_vias, those chains through a caller's
 //                            waypoints; connect_via.hpp, connect_via_multi.hpp)
 //
@@ -215,7 +216,8 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "refine.hpp"     // k_refine_search / k_refine_commit (+ _multi: RetainGrid) (Planner.refine_plan: shortcuts of a found plan)
 #include "connect.hpp"    // k_connect_search (+ _multi: ProtoTable, RetainGrid)      (Planner.connect_goal: goal chains from every tree node)
 #include "reach.hpp"      // k_reach_search                                           (Planner.goal_costs / retarget: those chains to MANY goals per launch)
-#include "connect_via.hpp" // k_connect_via_search / k_connect_via_commit                (Planner.connect_via: the same through a list of waypoints)
+#include "reach_multi.hpp" // k_reach_search_multi / k_reach_commit_multi                    (fleet_goal_costs / retargets: several trees per launch)
+#include "connect_via.hpp" // k_connect_via_search / k_connect_via_commit             (Planner.connect_via: the same through a list of waypoints)
 #include "connect_via_multi.hpp" // k_connect_via_search_multi / k_connect_via_commit_multi (connect_vias: several trees per launch)
 
 }  // namespace lq

@@ -755,6 +755,62 @@ class Engine(object):
         return Engine._commit_results(outs, counts, lambda k: "the chain of candidate (%d, %d) of engine %d does not reach the goal: "
                                       "nothing appended" % (cn[k], cj[k], k))
 
+    # -- several trees asked about many goals per call (csrc/engine_reach_multi.hpp) ---------
+    @staticmethod
+    def _targets_multi(engines, goals, buffers):
+        """One target table per engine as _targets makes it: (tables, pointers to the goals, the los, the his, the T_k)."""
+        n = len(engines)
+        goals, buffers = Engine._per_engine(goals, n, "goal table"), Engine._per_engine(buffers, n, "goal buffer (or one per goal)")
+        tabs = [e._targets(g, b) for e, g, b in zip(engines, goals, buffers)]
+        ptrs = [(C.c_void_p * n)(*[t[i].ctypes.data if len(t[i]) else None for t in tabs]) for i in range(3)]
+        return tabs, ptrs[0], ptrs[1], ptrs[2], np.ascontiguousarray([len(t[0]) for t in tabs], dtype=np.int32)
+
+    @staticmethod
+    def reach_search_multi(engines, goals, buffers, horizons, incumbents=None, goal_tries=8, nodes=None):
+        """reach_search for n engines in one native call (lqrrt_reach_search_multi): the searches of all trees for all their
+        targets share one kernel launch, every (engine, target) pair with a best key of its own.  `goals`: one table [T_k][n] per
+        engine; `buffers`: per engine one buffer, or one per goal; `horizons`: one per engine; `incumbents`: None, or one entry per
+        engine, each None (nothing to beat) or [T_k]; `goal_tries`: one for all or one per engine; `nodes`: None, or one entry per
+        engine, each None (every node) or an id list (an empty one: no candidates).  Returns a list, per engine, of
+        [(cost, node) or None] * T_k, each what that engine's own reach_search returns.  The engines share device and model; every
+        argument is checked before anything is launched, and nothing of any engine changes."""
+        engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
+        tabs, goal_ptrs, lo_ptrs, hi_ptrs, T = Engine._targets_multi(engines, goals, buffers)
+        incs, inc_ptrs = None, None
+        if incumbents is not None:
+            incs = [None if c is None else Engine._incumbents(c, int(T[k]), "goal")
+                    for k, c in enumerate(Engine._per_engine(incumbents, n, "incumbent list (or None)"))]
+            inc_ptrs = (C.c_void_p * n)(*[None if a is None or not len(a) else a.ctypes.data for a in incs])
+        ids, node_ptrs, counts_ptr = Engine._id_lists(nodes, n)
+        cost = [np.empty(max(int(t), 1), dtype=np.int64) for t in T]
+        node = [np.empty(max(int(t), 1), dtype=np.int32) for t in T]
+        cost_ptrs, out_ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in cost]), (C.c_void_p * n)(*[a.ctypes.data for a in node])
+        nat.check(nat.lib().lqrrt_reach_search_multi(handles, n, goal_ptrs, lo_ptrs, hi_ptrs, nat.ptr(T), node_ptrs, counts_ptr,
+                                                     nat.ptr(tries), nat.ptr(horizons), inc_ptrs, cost_ptrs, out_ptrs,
+                                                     engines[0]._stream()))
+        return [[None if node[k][t] < 0 else (int(cost[k][t]), int(node[k][t])) for t in range(int(T[k]))] for k in range(n)]
+
+    @staticmethod
+    def reach_commit_multi(engines, goals, buffers, nodes, horizons, goal_tries=8):
+        """reach_commit for n engines in one native call (lqrrt_reach_commit_multi): one workgroup per engine replays the chain of
+        its candidate nodes[k] toward its ONE target goals[k] with the box goals[k] -/+ buffers[k], below its own tree size (None:
+        the engine is left out and gets []).  Returns a list of new-id lists, None where the tree cannot hold the chain (that tree
+        is unchanged; the others commit).  A chain that does not reach its target raises NativeError(E_STATE) after the other
+        engines have committed; the error carries what they appended (`results`: this list, `failed`: the indices of the engines
+        that appended nothing for that reason).  The engines' own goals are not touched."""
+        engines, n, handles, horizons, tries = Engine._connect_multi_args(engines, horizons, goal_tries)
+        goals = [np.asarray(g, dtype=np.float64).reshape(1, -1) for g in Engine._per_engine(goals, n, "goal")]
+        tabs, goal_ptrs, lo_ptrs, hi_ptrs, T = Engine._targets_multi(engines, goals, buffers)
+        nodes = Engine._per_engine(nodes, n, "candidate")
+        if any(v is not None and int(v) < 0 for v in nodes):
+            raise ValueError("a candidate is a node id >= 0, or None")
+        cn = np.ascontiguousarray([-1 if v is None else int(v) for v in nodes], dtype=np.int32)
+        outs, out_ptrs, caps, counts = Engine._commit_outputs(tries)
+        nat.check(nat.lib().lqrrt_reach_commit_multi(handles, n, goal_ptrs, lo_ptrs, hi_ptrs, nat.ptr(cn), nat.ptr(tries),
+                                                     nat.ptr(horizons), out_ptrs, nat.ptr(caps), nat.ptr(counts), engines[0]._stream()))
+        return Engine._commit_results(outs, counts, lambda k: "the chain below node %d of engine %d does not reach the target: "
+                                      "nothing appended" % (cn[k], k))
+
     def push_samples(self, xs):
         xs = nat.as_f64(xs)
         if xs.ndim != 2 or xs.shape[1] != self.n:

@@ -723,6 +723,18 @@ class Planner:
                                                            bounds_error=False, fill_value=table[-1].copy()))
 
     # ------------------------------------------------------------------------------------------ one tree, many goals
+    def _goal_costs_targets(self, goals, goal_buffers):
+        """(goals [T][nstates], buffers) as goal_costs takes them, or ValueError; fleet_goal_costs asks every planner the same."""
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.ndim != 2 or goals.shape[1] != self.nstates or len(goals) < 1:
+            raise ValueError("Expected goals of shape (T, %d) with T >= 1." % self.nstates)
+        buffers = np.asarray(self.constraints.goal_buffer if goal_buffers is None else goal_buffers, dtype=np.float64)
+        if buffers.shape not in [(self.nstates,), (len(goals), self.nstates)]:
+            raise ValueError("Expected goal_buffers to be None, one buffer of %d entries, or one per goal." % self.nstates)
+        if not np.all(buffers >= 0):
+            raise ValueError("A goal buffer must not be negative.")
+        return goals, buffers
+
     def goal_costs(self, goals, goal_buffers=None, goal_tries=8, nodes=None):
         """
         What would it cost to go to each of these places instead?  Not in the reference.  The tree of the last plan is rooted at
@@ -741,14 +753,7 @@ class Planner:
         device (refine_plan's condition).  retarget(goals[t]) then makes goal t the planner's.
         """
         self._device_search_check("goal_costs", goal_tries)
-        goals = np.ascontiguousarray(goals, dtype=np.float64)
-        if goals.ndim != 2 or goals.shape[1] != self.nstates or len(goals) < 1:
-            raise ValueError("Expected goals of shape (T, %d) with T >= 1." % self.nstates)
-        buffers = np.asarray(self.constraints.goal_buffer if goal_buffers is None else goal_buffers, dtype=np.float64)
-        if buffers.shape not in [(self.nstates,), (len(goals), self.nstates)]:
-            raise ValueError("Expected goal_buffers to be None, one buffer of %d entries, or one per goal." % self.nstates)
-        if not np.all(buffers >= 0):
-            raise ValueError("A goal buffer must not be negative.")
+        goals, buffers = self._goal_costs_targets(goals, goal_buffers)
         run = self._refine_begin(need_goal=False)
         if run is None:
             return None
@@ -1294,6 +1299,105 @@ def connect_goals(planners, goal_tries=8, nodes=None, finish_on_goal=None):
             if ids is None:                                         # capacity (or a failed chain): this planner keeps what it has
                 continue
             planners[k]._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
+            results[k] = True
+        if failed is not None:
+            raise failed
+    return results
+
+
+def fleet_goal_costs(planners, goals, goal_buffers=None, goal_tries=8, nodes=None):
+    """
+    goal_costs for a fleet: the task-assignment matrix, P planners x T places, with the native calls shared.  `goals` is ONE array
+    [T][nstates] that every planner is asked about (berths, tasks); `goal_buffers` is None (each planner's own
+    constraints.goal_buffer), one buffer, or one per goal.  Returns (steps, nodes), two integer arrays of shape (P, T): row k is
+    exactly what planners[k].goal_costs(goals, goal_buffers, goal_tries, nodes[k]) returns, and all -1 where that returns None (no
+    tree of that planner on the device: it takes part in no launch).  The planners of one (device, native system type) form a
+    group; a group makes ONE search call over its trees (Engine.reach_search_multi: every (tree, goal) pair with a best key of its
+    own, so each entry is the one the planner's own search finds), in slices of 128.  `nodes`: None, or one entry per planner, each
+    None (every node) or an id list.  Reads only.  An assignment can be drawn from the matrix on the host; retargets() then gives
+    every planner its goal.
+
+    Refused with ValueError for EVERY planner before any is touched: a planner that appears twice, an object that is not a Planner,
+    a callback-mode planner, a tree that holds hand-added host nodes, goal_tries < 1, a `nodes` sequence of the wrong length, goals
+    not of shape (T, nstates) with T >= 1 for every planner's nstates, goal buffers of the wrong shape or negative.
+    """
+    planners, nodes = list(planners), None if nodes is None else list(nodes)
+    _fleet_check("fleet_goal_costs", planners, goal_tries, nodes)
+    goals = np.ascontiguousarray(goals, dtype=np.float64)
+    if goals.ndim != 2 or len(goals) < 1:
+        raise ValueError("fleet_goal_costs: expected goals of shape (T, nstates) with T >= 1.")
+    buffers = []
+    for k, p in enumerate(planners):
+        if p.nstates != goals.shape[1]:
+            raise ValueError("fleet_goal_costs: planner %d has %d states, the goals have %d." % (k, p.nstates, goals.shape[1]))
+        buffers.append(p._goal_costs_targets(goals, goal_buffers)[1])
+    runs = _fleet_begin("fleet_goal_costs", planners, lambda p: p._refine_begin(need_goal=False))
+    steps = np.full((len(planners), len(goals)), -1, dtype=np.int64)
+    start = np.full((len(planners), len(goals)), -1, dtype=np.int64)
+    for mine in _fleet_groups(planners, runs):
+        wins = Engine.reach_search_multi([planners[k]._engine for k in mine], [goals] * len(mine), [buffers[k] for k in mine],
+                                         [runs[k].H for k in mine], None, goal_tries, None if nodes is None else [nodes[k] for k in mine])
+        for k, row in zip(mine, wins):
+            for t, w in enumerate(row):
+                if w is not None:
+                    steps[k, t], start[k, t] = w
+    return steps, start
+
+
+def retargets(planners, goals, goal_tries=8, nodes=None, finish_on_goal=None):
+    """
+    retarget for a fleet: every planner gets exactly what its own retarget(goals[k], goal_tries, nodes[k], finish_on_goal) gives it --
+    the appended tree nodes, node_seq, x_seq, u_seq, t_seq, T, plan_reached_goal, planner.goal and the engine's goal and box, the
+    interpolators, a finish_on_goal node dropped and steered again; on False everything unchanged -- but the native calls are shared.
+    `goals`: one entry per planner, its new goal [nstates] or None: that planner sits out and gets False.  The planners whose goal is
+    the one their tree was grown for (and still is theirs) go together through connect_goals, as retarget hands them to connect_goal.
+    The others form groups by (device, native system type); a group makes ONE search call over its trees with one target each
+    (Engine.reach_search_multi) and ONE commit call over those with a winner (Engine.reach_commit_multi), in slices of 128.
+    `nodes`: None, or one entry per planner, each None (every node) or an id list.  Returns the list of bools.
+
+    Refused with ValueError for EVERY planner before any is touched: everything connect_goals refuses but a changed goal, a `goals`
+    sequence of the wrong length, a goal not of shape (nstates,).  If a native call fails, the planners that did commit adopt their
+    plans and goals -- those of the failing commit call included -- then the error is raised.
+    """
+    planners, goals, nodes = list(planners), list(goals), None if nodes is None else list(nodes)
+    if len(goals) != len(planners):
+        raise ValueError("retargets: expected one goal (or None) per planner.")
+    _fleet_check("retargets", planners, goal_tries, nodes)
+    new = []
+    for k, (p, g) in enumerate(zip(planners, goals)):
+        g = None if g is None else np.array(g, dtype=np.float64)
+        if g is not None and g.shape != (p.nstates,):
+            raise ValueError("retargets: the goal of planner %d must have the dimensionality of its state space." % k)
+        new.append(g)
+    runs = _fleet_begin("retargets", planners, lambda p: p._refine_begin(need_goal=False))
+    runs = [None if g is None else run for g, run in zip(new, runs)]
+    results = [False] * len(planners)
+    # where retarget is connect_goal: the goal the tree was grown for, still the planner's
+    same = [k for k, (p, g) in enumerate(zip(planners, new)) if runs[k] is not None and p.goal is not None
+            and np.array_equal(g, p._grown_goal) and np.array_equal(p.goal, p._grown_goal)]
+    if same:
+        for k, ok in zip(same, connect_goals([planners[k] for k in same], goal_tries, None if nodes is None else [nodes[k] for k in same],
+                                             finish_on_goal)):
+            results[k] = ok
+            runs[k] = None
+    for mine in _fleet_groups(planners, runs):
+        buffs = dict((k, planners[k].constraints.goal_buffer) for k in mine)
+        wins = Engine.reach_search_multi([planners[k]._engine for k in mine], [new[k][None, :] for k in mine], [buffs[k] for k in mine],
+                                         [runs[k].H for k in mine], None, goal_tries, None if nodes is None else [nodes[k] for k in mine])
+        winners = [(k, w[0]) for k, w in zip(mine, wins) if w[0] is not None]
+        if not winners:
+            continue
+        ids_of, failed = _fleet_commit(lambda: Engine.reach_commit_multi(
+            [planners[k]._engine for k, _ in winners], [new[k] for k, _ in winners], [buffs[k] for k, _ in winners],
+            [w[1] for _, w in winners], [runs[k].H for k, _ in winners], goal_tries))
+        for (k, w), ids in zip(winners, ids_of):
+            if ids is None:                                         # capacity (or a failed chain): this planner keeps what it has
+                continue
+            p = planners[k]
+            p.set_goal(new[k])                                      # (retarget's steps, in retarget's order)
+            p._engine_resolution(p._engine)
+            p._grown_goal = np.array(p.goal, dtype=np.float64)
+            p._connect_accept(runs[k], w[0], w[1], ids, finish_on_goal)
             results[k] = True
         if failed is not None:
             raise failed
