@@ -299,6 +299,35 @@ int lqrrt_tree_retain(lqrrt_engine* e, int new_root, int revalidate, lqrrt_retai
 int lqrrt_tree_retain_multi(lqrrt_engine** engines, int n, const int32_t* new_roots, const int32_t* revalidate,
                             lqrrt_retain_stats* out, int32_t** old_to_new_host, void* stream);
 
+/* Which plans in the tree stay clear of obstacles that MOVE (Planner.avoid): D discs of radii radii_host[D] whose centres
+ * tracks_host [L][D][2] (world x, y) are given at L consecutive instants spaced by the engine's dt; row `start` >= 0 of the
+ * table coincides with the root's row, and a track that has ended stays where it ended (row min(tau, L - 1)).  The rule
+ * (tests/clear_reference.py): cum[0] = edge length of the root, cum[i] = cum[pID[i]] + edge length of i;
+ * row k of node i > 0 has time index tau = start + cum[pID[i]] + k, the root's row tau = start.  A row is tested with the
+ * model's feasibility test against the D discs of its instant and nothing else -- no static obstacle, no occupancy grid -- each
+ * disc a circular obstacle exactly as the static map derives one (the novice boats' inflation included).
+ *   first[i]  = the smallest tau of a failing row over the edges of the nodes from i up to and including the root, or -1
+ *   dwell[i]  = for a goal hit (a non-root node strictly inside the current goal box): the smallest tau' with
+ *               start + cum[i] - 1 < tau' <= L - 1 at which its last row fails against the discs of tau', or -1; -2 for any other node
+ *   best      = the hit with first == -1 and dwell == -1 that has the fewest steps cum, lowest id on ties
+ * first_host / dwell_host [tree size] (or NULL) receive the per-node arrays.  The tree is not modified: pools, parents, ignore
+ * set, lqrrt_plan_best, sample stream and counters stay as they were; all device memory of the call is transient and
+ * lqrrt_engine_footprint is the same before and after.  Synchronous.  Every argument is checked before anything is enqueued:
+ * LQRRT_E_ARG for L < 1, D < 1, start < 0, a position that is not finite, a radius that is not >= 0, start + the deepest cum
+ * beyond 31 bits, or hull points that do not fit in a workgroup's LDS; LQRRT_E_STATE for no tree, no goal, or a model whose
+ * feasibility test has no circle path (the pendulums, the double integrator, LQRRT_MODEL_GENERIC, an out-of-tree model that
+ * does not declare DISCS). */
+typedef struct {
+    int32_t size;             /* nodes of the tree                                            */
+    int32_t conflicts;        /* nodes with a failing row on their own edge                   */
+    int32_t blocked;          /* nodes whose own edge is clear and an ancestor's is not       */
+    int32_t hits, clear_hits; /* goal hits; those with first == -1 and dwell == -1            */
+    int32_t best_end;         /* -1 without a clear hit                                       */
+    int64_t best_steps;       /* cum of best_end; -1 without a clear hit                      */
+} lqrrt_clear_stats;
+int lqrrt_tree_clear(lqrrt_engine* e, const double* tracks_host, const double* radii_host, int L, int D, int start,
+                     lqrrt_clear_stats* out, int32_t* first_host, int32_t* dwell_host, void* stream);
+
 /* Overwrites the ignore bits of nodes [first, first+count) (planner.py:270 `ignores`). */
 int lqrrt_tree_set_ignored(lqrrt_engine* e, int first, int count, const uint8_t* flags_host);
 

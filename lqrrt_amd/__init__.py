@@ -14,14 +14,15 @@ the native problem plugins (systems), update_plans (several planners through sha
 trees -- planner.py), refine_plans (their found plans shortened through shared calls), connect_goals (the plans whose
 budget ran out before a goal hit connected to the goal through shared calls), connect_vias (the same through each planner's own
 list of waypoints), fleet_goal_costs (what every planner's tree would pay to reach each of a shared list of places, one matrix
-through shared calls) and retargets (every planner given a new goal from the tree it holds, through shared calls).  Importing works
-without a GPU; computing does not.
+through shared calls), retargets (every planner given a new goal from the tree it holds, through shared calls) and deconflict
+(prioritised planning over the trees as they stand: every planner picks the best plan of its tree that stays clear of the plans of
+those before it, Planner.avoid).  Importing works without a GPU; computing does not.
 """
 from .constraints import Constraints
-from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias, fleet_goal_costs, retargets
+from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias, fleet_goal_costs, retargets, deconflict
 from .tree import Tree
 from . import systems
 from . import dare
 
 __all__ = ["Constraints", "Planner", "Tree", "systems", "dare", "update_plans", "refine_plans", "connect_goals", "connect_vias",
-           "fleet_goal_costs", "retargets"]
+           "fleet_goal_costs", "retargets", "deconflict"]

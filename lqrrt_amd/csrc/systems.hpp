@@ -280,6 +280,7 @@ __device__ __forceinline__ bool hull_hits(const GeoL& g, double px, double py, d
 
 struct BoatCommon {
     static constexpr int N = 6, M = 3, NW = 1;
+    static constexpr bool DISCS = true;              // feasible has a circle path: k_clear_check (clear.hpp) can hand it moving discs
     __host__ __device__ __forceinline__ static constexpr int wd(int) { return 2; }
 
     // K = [kp R(h)' | kd] with diagonal kp, kd (demo_boat_advanced.py:139-151)
@@ -779,6 +780,7 @@ struct RosBoat : BoatCommon {
 struct Car {
     static constexpr bool TWO_WAVEFRONTS = true;     // k_steer: a second wavefront runs the step tests
     static constexpr int N = 5, M = 2, NW = 1;
+    static constexpr bool DISCS = true;              // (as BoatCommon's)
     __host__ __device__ static constexpr int wd(int) { return 2; }
     // params: 0 invM[2] | 2 D[2] | 4 u_lo[2] | 6 u_hi[2] | 8 velmax0 | 9 kp[2] | 11 kd[2]
     __device__ static void gain(const double* P, const double*, const double* trig, const double*, double* K) {

@@ -243,6 +243,57 @@ class Engine(object):
             e.generation += 1             # bound Tree views of the old numbering are dead
         return [(stats[i].as_dict(), maps[i][:stats[i].old_size]) for i in range(n)]
 
+    @staticmethod
+    def track_table(tracks, radii, start=0):
+        """(tracks [L][D][2], radii [D], start) as lqrrt_tree_clear takes them, or ValueError.  `tracks` is an array (L, D, 2) -- D
+        discs at L consecutive instants -- or a list of D arrays (L_d, 2), each padded to the longest by holding its last row;
+        `radii` is one radius for all or one per disc.  Host only."""
+        if isinstance(tracks, (list, tuple)):
+            rows = [np.asarray(t, dtype=np.float64) for t in tracks]
+            if len(rows) < 1 or any(t.ndim != 2 or t.shape[1] != 2 or len(t) < 1 for t in rows):
+                raise ValueError("Expected tracks as an array (L, D, 2) or a list of D >= 1 arrays (L_d >= 1, 2).")
+            L = max(len(t) for t in rows)
+            table = np.empty((L, len(rows), 2))
+            for d, t in enumerate(rows):
+                table[:len(t), d] = t
+                table[len(t):, d] = t[-1]                         # a track that has ended stays where it ended
+        else:
+            table = np.ascontiguousarray(tracks, dtype=np.float64)
+        if table.ndim != 3 or table.shape[2] != 2 or table.shape[0] < 1 or table.shape[1] < 1:
+            raise ValueError("Expected tracks as an array (L, D, 2) with L >= 1 and D >= 1, or a list of D arrays (L_d, 2).")
+        if not np.all(np.isfinite(table)):
+            raise ValueError("A track position is not finite.")
+        D = table.shape[1]
+        r = np.asarray(radii, dtype=np.float64)
+        if r.shape not in [(), (D,)]:
+            raise ValueError("Expected radii to be one radius or one per disc (%d)." % D)
+        r = np.ascontiguousarray(np.broadcast_to(r, (D,)))
+        if not np.all(r >= 0):
+            raise ValueError("A radius must be >= 0.")
+        if int(start) != start or int(start) < 0:
+            raise ValueError("start must be an integer >= 0.")
+        return np.ascontiguousarray(table), r, int(start)
+
+    def tree_clear(self, tracks, radii, start=0, per_node=False):
+        """Which plans of the tree stay clear of moving discs (lqrrt_tree_clear; the rule: tests/clear_reference.py).  `tracks`,
+        `radii`: what track_table takes -- the discs' centres at consecutive instants spaced by the engine's dt; row `start` of
+        the table coincides with the root's row.  Returns the counters (dict: size, conflicts, blocked, hits, clear_hits, best_end,
+        best_steps), and with `per_node` also first [N] and dwell_first [N] (int32: the time index of the first conflict on a
+        node's root path, -1 = clear; for a goal hit the first conflict while it waits at the goal, -1 = none, -2 = not a hit).
+        Reads only: tree, goal bookkeeping and footprint stay as they are."""
+        table, r, start = self.track_table(tracks, radii, start)
+        st = nat.ClearStats()
+        first = dwell = None
+        if per_node:
+            n = max(self.size, 1)
+            first, dwell = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_tree_clear(self.h, nat.ptr(table), nat.ptr(r), table.shape[0], table.shape[1], start, C.byref(st),
+                                             None if first is None else nat.ptr(first), None if dwell is None else nat.ptr(dwell),
+                                             self._stream()))
+        if per_node:
+            return st.as_dict(), first[:st.size], dwell[:st.size]
+        return st.as_dict()
+
     def tree_truncate(self, size):
         nat.check(nat.lib().lqrrt_tree_truncate(self.h, int(size)))
         self.epoch += 1

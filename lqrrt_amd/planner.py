@@ -797,6 +797,51 @@ class Planner:
         self._connect_accept(run, cost, node, ids, finish_on_goal)
         return True
 
+    # ------------------------------------------------------------------------------------------ moving obstacles
+    def avoid(self, tracks, radii, start=0, adopt=True):
+        """
+        Which plan in the tree stays clear of obstacles that move?  Not in the reference, whose ROS node re-evaluates its one
+        plan on the host.  `tracks` gives the centres (world x, y) of D discs at consecutive instants spaced by `dt`: an array
+        (L, D, 2), or a list of D arrays (L_d, 2), each held at its last row once it has ended (a vehicle that has arrived sits
+        in its berth); `radii` is one radius or one per disc; row `start` of the tracks coincides with the plan's first row.
+        Every recorded row of every edge of the tree is tested at ITS time -- its index in a plan's x_seq plus `start` -- with the
+        system's feasibility test against the discs of that instant alone (no static map: the tree's edges passed that when
+        they were grown), and every goal hit is tested at its last row for as long as the tracks go on after it has arrived.
+        The best plan is the goal hit whose whole root path and whose wait at the goal stay clear, fewest steps first, lowest
+        node id on ties.  One call on the device (csrc/clear.hpp); tests/clear_reference.py restates the rule.
+
+        Returns a dict: size, conflicts (nodes with a conflict on their own edge), blocked (clear themselves, below a
+        conflict), hits, clear_hits, best_end, best_steps (-1: no clear hit) and plan_first -- the time in seconds, from the
+        plan's first row, of the first conflict on the CURRENT plan (en route or, for a plan that reached the goal, while it waits
+        there; a finish_on_goal tail is not part of the check), None when that plan is clear.  With `adopt` and a clear hit the
+        plan becomes that hit's root path (node_seq, x_seq, u_seq, t_seq, T, the interpolators) and plan_reached_goal is set; a
+        finish_on_goal tail is not applied to it, because it would not have been checked.  Otherwise the plan is untouched.
+        The tree is never modified.  Returns None when there is no tree of this planner on the device (refine_plan's condition).
+        Not covered: chains that connect_goal / connect_via / retarget appended are tested like any other edge, but nothing is
+        appended here; waiting at the start; obstacles that are not discs.
+        """
+        if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
+            raise NotImplementedError("avoid: in callback mode the feasibility test is the user's Python function; the device "
+                                      "cannot call it on the rows of the tree.")
+        table, radii, start = Engine.track_table(tracks, radii, start)
+        run = self._refine_begin(need_goal=False)
+        if run is None:
+            return None
+        if self.goal is None or not np.array_equal(self.goal, self._grown_goal):
+            raise RuntimeError("avoid: the goal changed since the tree was grown; use update_plan, replan or retarget.")
+        out, first, dwell = self._engine.tree_clear(table, radii, start, per_node=True)
+        end = run.core[-1]
+        taus = [int(first[end])] + ([int(dwell[end])] if self.plan_reached_goal else [])
+        taus = [t for t in taus if t >= 0]
+        out["plan_first"] = (min(taus) - start) * self.dt if taus else None
+        if adopt and out["best_end"] >= 0:
+            if run.finish:
+                self.tree._drop_host_tail()                         # (the tail of the replaced plan; none is steered for the new one)
+            self._adopt_plan(out["best_end"])
+            self.plan_reached_goal = True
+            self._prepare_interpolators()
+        return out
+
     # ------------------------------------------------------------------------------------------ setters
     def set_goal(self, goal):
         """New goal state and goal region (planner.py:468-487); update the plan afterwards."""
@@ -1401,4 +1446,54 @@ def retargets(planners, goals, goal_tries=8, nodes=None, finish_on_goal=None):
             results[k] = True
         if failed is not None:
             raise failed
+    return results
+
+
+def deconflict(planners, radii, order=None, start=0):
+    """
+    Prioritised planning over the trees as they stand: in `order` (default: as listed) every planner picks, with Planner.avoid, the
+    best plan of its tree that stays clear of the plans of the planners before it -- each of those a disc of its radius that moves
+    along its plan's x_seq[:, :2] and then sits where it arrived.  `radii`: one radius for every vehicle, or one per planner (in the
+    order of `planners`).  `start` is avoid's: row `start` of the earlier plans coincides with a later planner's first row (0: all
+    plans begin at the same instant).  The first planner of the order has nothing to avoid and is not asked.  A planner without a
+    clear hit keeps its plan, is reported as such (best_end -1), and still counts as a track for the later ones.
+
+    Returns one entry per planner, in the order of `planners`: avoid's dict, or None for the first of the order and for a planner
+    without a tree on the device.  It costs one device call per planner after the first: a planner's tracks are the plans the
+    earlier ones ended up with, so the priority order makes the calls sequential by nature; nothing is batched across planners.
+
+    Refused with ValueError before any planner is touched: planners that do not share `dt`, a planner twice, an `order` that is no
+    permutation, `radii` of the wrong shape or negative, a planner without a plan (it cannot be a track).  Callback mode raises
+    NotImplementedError, as avoid does.
+    """
+    planners = list(planners)
+    n = len(planners)
+    order = list(range(n)) if order is None else [int(k) for k in order]
+    if sorted(order) != list(range(n)):
+        raise ValueError("deconflict: order must be a permutation of the planners' indices.")
+    if len(set(id(p) for p in planners)) != n:
+        raise ValueError("deconflict: a planner appears twice.")
+    r = np.asarray(radii, dtype=np.float64)
+    if r.shape not in [(), (n,)]:
+        raise ValueError("deconflict: expected one radius, or one per planner.")
+    r = np.broadcast_to(r, (n,))
+    if not np.all(r >= 0):
+        raise ValueError("deconflict: a radius must be >= 0.")
+    if int(start) != start or int(start) < 0:
+        raise ValueError("deconflict: start must be an integer >= 0.")
+    for k, p in enumerate(planners):
+        if p.callback_mode:
+            raise NotImplementedError("deconflict: planner %d is in callback mode; the device cannot call its Python feasibility test." % k)
+    if any(p.dt != planners[0].dt for p in planners):
+        raise ValueError("deconflict: the planners must share dt (the tracks are sampled at it).")
+    for k, p in enumerate(planners):
+        if getattr(p, "x_seq", None) is None or len(p.x_seq) < 1:
+            raise ValueError("deconflict: planner %d has no plan; it cannot be a track." % k)
+    results = [None] * n
+    for at, k in enumerate(order):
+        if at == 0:
+            continue
+        before = order[:at]
+        tracks = [np.asarray(planners[j].x_seq, dtype=np.float64)[:, :2] for j in before]
+        results[k] = planners[k].avoid(tracks, r[before], start)
     return results
