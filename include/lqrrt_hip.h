@@ -328,6 +328,36 @@ typedef struct {
 int lqrrt_tree_clear(lqrrt_engine* e, const double* tracks_host, const double* radii_host, int L, int D, int start,
                      lqrrt_clear_stats* out, int32_t* first_host, int32_t* dwell_host, void* stream);
 
+/* lqrrt_tree_clear for `waits` departure delays at once (Planner.avoid with max_wait): the vehicle may hold the root's row for
+ * w = 0 .. waits - 1 rows of dt before it leaves, 1 <= waits <= 64, and every per-node answer is a 64-bit mask over w.  Tracks,
+ * radii, L, D, start, cum, the clamp min(tau, L - 1), the row test and the goal hit are lqrrt_tree_clear's.  The rule
+ * (tests/clear_wait_reference.py), for delay w:
+ *   wait       the root's row is tested at every tau = start .. start + w; root_ok bit w = all of them pass (so root_ok is
+ *              prefix-closed: above a 0 bit every bit is 0)
+ *   edges      row k of node i > 0 has tau = start + w + cum[pID[i]] + k; own_ok[i] bit w = every row of i's edge passes;
+ *              own_ok[0] = root_ok
+ *   clear[i]   = own_ok[i] & clear[pID[i]]: the AND over the nodes from i up to and including the root
+ *   dwell_ok[i] for a goal hit: bit w = its last row passes at every tau' in [start + w + cum[i], L - 1] (an empty range passes);
+ *              0 for any other node
+ *   best       over hits i and delays w set in clear[i] & dwell_ok[i]: the smallest (w + cum[i], i)
+ * Bit w of clear[i] is therefore (first[i] == -1 of lqrrt_tree_clear at start + w) && root_ok bit w, and bit w of dwell_ok[i] is
+ * (dwell[i] == -1 of that call).  clear_host / dwell_host [tree size] (or NULL) receive the per-node masks.  Reads only and
+ * synchronous, as lqrrt_tree_clear: all device memory of the call is transient.  Every argument is checked before anything is
+ * enqueued: lqrrt_tree_clear's refusals, LQRRT_E_ARG for waits outside 1 .. 64, and LQRRT_E_ARG when
+ * start + (waits - 1) + the deepest cum goes beyond 31 bits. */
+typedef struct {
+    int32_t size;             /* nodes of the tree                                                    */
+    int32_t hits;             /* goal hits                                                            */
+    int32_t clear_hits;       /* hits with clear & dwell_ok != 0: clear at some delay                 */
+    int32_t clear_now;        /* hits with bit 0 set in both: lqrrt_tree_clear's clear_hits           */
+    int32_t best_end;         /* -1 without a clear hit                                               */
+    int32_t best_wait;        /* the delay of the best; -1 without                                    */
+    int64_t best_steps;       /* cum of best_end, without the wait; -1 without                        */
+    int64_t best_arrival;     /* best_wait + best_steps; -1 without                                   */
+} lqrrt_clear_wait_stats;
+int lqrrt_tree_clear_wait(lqrrt_engine* e, const double* tracks_host, const double* radii_host, int L, int D, int start, int waits,
+                          lqrrt_clear_wait_stats* out, uint64_t* clear_host, uint64_t* dwell_host, void* stream);
+
 /* Overwrites the ignore bits of nodes [first, first+count) (planner.py:270 `ignores`). */
 int lqrrt_tree_set_ignored(lqrrt_engine* e, int first, int count, const uint8_t* flags_host);
 

@@ -72,6 +72,14 @@ class ClearStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ClearWaitStats(C.Structure):
+    _fields_ = [("size", C.c_int32), ("hits", C.c_int32), ("clear_hits", C.c_int32), ("clear_now", C.c_int32),
+                ("best_end", C.c_int32), ("best_wait", C.c_int32), ("best_steps", C.c_int64), ("best_arrival", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/lqrrt_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I, _I64, _D = C.c_int, C.c_int64, C.c_double
@@ -101,6 +109,7 @@ SIGNATURES = {
     "lqrrt_tree_retain": (_I, [_P, _I, _I, C.POINTER(RetainStats), _P, _P]),
     "lqrrt_tree_retain_multi": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "lqrrt_tree_clear": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(ClearStats), _P, _P, _P]),
+    "lqrrt_tree_clear_wait": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(ClearWaitStats), _P, _P, _P]),
     "lqrrt_tree_get_edges": (_I, [_P, _I, _I, _P, _P]),
     "lqrrt_tree_mark": (_I, [_P]),
     "lqrrt_tree_rewind": (_I, [_P]),

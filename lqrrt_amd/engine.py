@@ -294,6 +294,36 @@ class Engine(object):
             return st.as_dict(), first[:st.size], dwell[:st.size]
         return st.as_dict()
 
+    @staticmethod
+    def wait_count(waits, what="waits", lo=1, hi=64):
+        """`waits` as an integer in lo .. hi, or ValueError.  Host only."""
+        if isinstance(waits, (bool, np.bool_)) or not isinstance(waits, (int, np.integer)) or not lo <= int(waits) <= hi:
+            raise ValueError("%s must be an integer in %d .. %d." % (what, lo, hi))
+        return int(waits)
+
+    def tree_clear_wait(self, tracks, radii, start=0, waits=1, per_node=False):
+        """tree_clear for the departure delays w = 0 .. waits - 1 at once, 1 <= waits <= 64 (lqrrt_tree_clear_wait; the rule:
+        tests/clear_wait_reference.py): the vehicle holds the root's row for w rows of dt, tested there at every instant of the
+        wait, and then follows the tree w rows later.  `tracks`, `radii`, `start`: what track_table takes.  Returns the counters
+        (dict: size, hits, clear_hits -- hits that are clear at some delay --, clear_now -- at delay 0: tree_clear's clear_hits --,
+        best_end, best_wait, best_steps -- without the wait --, best_arrival = best_wait + best_steps; -1 without a best), and with
+        `per_node` also clear [N] and dwell_ok [N] (uint64: bit w of clear = the node's root path and the wait before it are clear
+        at delay w; bit w of dwell_ok = a goal hit can wait at the goal from its arrival at delay w on, 0 for a node that is no
+        hit).  Reads only: tree, goal bookkeeping and footprint stay as they are."""
+        table, r, start = self.track_table(tracks, radii, start)
+        waits = self.wait_count(waits)
+        st = nat.ClearWaitStats()
+        clear = dwell = None
+        if per_node:
+            n = max(self.size, 1)
+            clear, dwell = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
+        nat.check(nat.lib().lqrrt_tree_clear_wait(self.h, nat.ptr(table), nat.ptr(r), table.shape[0], table.shape[1], start, waits,
+                                                  C.byref(st), None if clear is None else nat.ptr(clear),
+                                                  None if dwell is None else nat.ptr(dwell), self._stream()))
+        if per_node:
+            return st.as_dict(), clear[:st.size], dwell[:st.size]
+        return st.as_dict()
+
     def tree_truncate(self, size):
         nat.check(nat.lib().lqrrt_tree_truncate(self.h, int(size)))
         self.epoch += 1

@@ -58,6 +58,8 @@ class Planner:
         (ValueError when they disagree).  None: the probe alone decides (lqrrt_amd/callback.py classify_erf).
     """
 
+    plan_wait = 0                          # rows of dt the current plan stands on its first row before it leaves (avoid(max_wait))
+
     def __init__(self, dynamics, lqr, constraints,
                  horizon, dt=0.05, FPR=0,
                  error_tol=0.05, erf=np.subtract,
@@ -363,7 +365,7 @@ class Planner:
         (replan) where the reference's loop takes get_state(next_runtime).  Host only."""
         if getattr(self, "node_seq", None) is None or self.tree is None:
             raise RuntimeError("plan_node_after: there is no plan.")
-        steps = 0
+        steps = self.plan_wait                                      # (rows of a wait at the start: avoid(max_wait))
         for k, node in enumerate(self.node_seq):
             steps += len(self.tree.x_seq[int(node)])
             t_k = (steps - 1) * self.dt                             # the node's state is the last row of its edge
@@ -475,6 +477,7 @@ class Planner:
         self.x_seq, self.u_seq = self.tree.trajectory(self.node_seq)
         self.T = len(self.x_seq) * self.dt
         self.t_seq = np.arange(len(self.x_seq)) * self.dt
+        self.plan_wait = 0                                          # (only avoid(max_wait) puts wait rows in front)
 
     def _finish_on_goal(self):
         """
@@ -798,7 +801,7 @@ class Planner:
         return True
 
     # ------------------------------------------------------------------------------------------ moving obstacles
-    def avoid(self, tracks, radii, start=0, adopt=True):
+    def avoid(self, tracks, radii, start=0, adopt=True, max_wait=0):
         """
         Which plan in the tree stays clear of obstacles that move?  Not in the reference, whose ROS node re-evaluates its one
         plan on the host.  `tracks` gives the centres (world x, y) of D discs at consecutive instants spaced by `dt`: an array
@@ -818,26 +821,59 @@ class Planner:
         finish_on_goal tail is not applied to it, because it would not have been checked.  Otherwise the plan is untouched.
         The tree is never modified.  Returns None when there is no tree of this planner on the device (refine_plan's condition).
         Not covered: chains that connect_goal / connect_via / retarget appended are tested like any other edge, but nothing is
-        appended here; waiting at the start; obstacles that are not discs.
+        appended here; waiting anywhere but at the start; obstacles that are not discs.
+
+        `max_wait` in 1 .. 63 also asks "and if I left later?": the vehicle may stand on the plan's first row (the root's) for
+        w = 0 .. max_wait rows of dt and follow the tree w rows later; while it stands there the root's row is tested at every
+        instant of the wait.  This is meant for a vehicle that can hold station -- as the wait at the goal already assumes.
+        All delays are answered by one call on the device (csrc/clear_wait.hpp; tests/clear_wait_reference.py restates the rule).
+        The best plan is then the clear (goal hit, delay) that arrives first, wait included -- lowest node id on ties, and of one
+        node its shortest clear delay.  The dict holds size, hits, clear_hits (hits that are clear at some delay), clear_now (at
+        delay 0: what clear_hits is without max_wait), best_end, best_wait, best_steps (without the wait), best_arrival
+        (= best_wait + best_steps) and plan_first, which is None when the current plan is clear as it stands (with the wait it was
+        adopted with) and otherwise comes from one more call of the plain query.  On adoption `best_wait` copies of the plan's
+        first x_seq and u_seq rows stand in front of it: node_seq is the tree path as ever, T, t_seq and the interpolators go
+        over the longer sequence, and `plan_wait` = best_wait says how many rows are the wait (0 after every other call that sets
+        a plan).  With max_wait = 0 the call, its cost and its dict are what they were.
         """
         if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
             raise NotImplementedError("avoid: in callback mode the feasibility test is the user's Python function; the device "
                                       "cannot call it on the rows of the tree.")
         table, radii, start = Engine.track_table(tracks, radii, start)
+        max_wait = Engine.wait_count(max_wait, "max_wait", 0, 63)
         run = self._refine_begin(need_goal=False)
         if run is None:
             return None
         if self.goal is None or not np.array_equal(self.goal, self._grown_goal):
             raise RuntimeError("avoid: the goal changed since the tree was grown; use update_plan, replan or retarget.")
-        out, first, dwell = self._engine.tree_clear(table, radii, start, per_node=True)
         end = run.core[-1]
-        taus = [int(first[end])] + ([int(dwell[end])] if self.plan_reached_goal else [])
-        taus = [t for t in taus if t >= 0]
-        out["plan_first"] = (min(taus) - start) * self.dt if taus else None
+        if max_wait == 0:
+            out, first, dwell = self._engine.tree_clear(table, radii, start, per_node=True)
+        else:
+            out, clear, dwell_ok = self._engine.tree_clear_wait(table, radii, start, max_wait + 1, per_node=True)
+            now = self.plan_wait                                    # the current plan leaves after the wait it was adopted with
+            bit = (1 << now) if now <= max_wait else 0
+            if int(clear[end]) & bit and (not self.plan_reached_goal or int(dwell_ok[end]) & bit):
+                first = dwell = None
+            else:                                                   # the time of its first conflict: the plain query, once
+                _, first, dwell = self._engine.tree_clear(table, radii, start + now, per_node=True)
+        if first is None:
+            out["plan_first"] = None
+        else:
+            taus = [int(first[end])] + ([int(dwell[end])] if self.plan_reached_goal else [])
+            taus = [t for t in taus if t >= 0]
+            out["plan_first"] = (min(taus) - start) * self.dt if taus else None
         if adopt and out["best_end"] >= 0:
             if run.finish:
                 self.tree._drop_host_tail()                         # (the tail of the replaced plan; none is steered for the new one)
             self._adopt_plan(out["best_end"])
+            wait = out.get("best_wait", 0)
+            if wait > 0:                                            # stand on the first row, then go
+                self.x_seq = [np.array(self.x_seq[0]) for _ in range(wait)] + list(self.x_seq)
+                self.u_seq = [np.array(self.u_seq[0]) for _ in range(wait)] + list(self.u_seq)
+                self.T = len(self.x_seq) * self.dt
+                self.t_seq = np.arange(len(self.x_seq)) * self.dt
+                self.plan_wait = wait
             self.plan_reached_goal = True
             self._prepare_interpolators()
         return out
@@ -1449,21 +1485,24 @@ def retargets(planners, goals, goal_tries=8, nodes=None, finish_on_goal=None):
     return results
 
 
-def deconflict(planners, radii, order=None, start=0):
+def deconflict(planners, radii, order=None, start=0, max_wait=0):
     """
     Prioritised planning over the trees as they stand: in `order` (default: as listed) every planner picks, with Planner.avoid, the
     best plan of its tree that stays clear of the plans of the planners before it -- each of those a disc of its radius that moves
     along its plan's x_seq[:, :2] and then sits where it arrived.  `radii`: one radius for every vehicle, or one per planner (in the
     order of `planners`).  `start` is avoid's: row `start` of the earlier plans coincides with a later planner's first row (0: all
     plans begin at the same instant).  The first planner of the order has nothing to avoid and is not asked.  A planner without a
-    clear hit keeps its plan, is reported as such (best_end -1), and still counts as a track for the later ones.
+    clear hit keeps its plan, is reported as such (best_end -1), and still counts as a track for the later ones.  `max_wait` is
+    avoid's too: a planner may leave up to max_wait rows of dt late ("the other one crosses my short branch: I leave two ticks
+    later"); the rows of its wait stand in its x_seq, so the planners after it see it waiting at its start.
 
     Returns one entry per planner, in the order of `planners`: avoid's dict, or None for the first of the order and for a planner
     without a tree on the device.  It costs one device call per planner after the first: a planner's tracks are the plans the
     earlier ones ended up with, so the priority order makes the calls sequential by nature; nothing is batched across planners.
 
     Refused with ValueError before any planner is touched: planners that do not share `dt`, a planner twice, an `order` that is no
-    permutation, `radii` of the wrong shape or negative, a planner without a plan (it cannot be a track).  Callback mode raises
+    permutation, `radii` of the wrong shape or negative, a `max_wait` that is no integer in 0 .. 63, a planner without a plan (it
+    cannot be a track).  Callback mode raises
     NotImplementedError, as avoid does.
     """
     planners = list(planners)
@@ -1481,6 +1520,7 @@ def deconflict(planners, radii, order=None, start=0):
         raise ValueError("deconflict: a radius must be >= 0.")
     if int(start) != start or int(start) < 0:
         raise ValueError("deconflict: start must be an integer >= 0.")
+    max_wait = Engine.wait_count(max_wait, "deconflict: max_wait", 0, 63)
     for k, p in enumerate(planners):
         if p.callback_mode:
             raise NotImplementedError("deconflict: planner %d is in callback mode; the device cannot call its Python feasibility test." % k)
@@ -1495,5 +1535,5 @@ def deconflict(planners, radii, order=None, start=0):
             continue
         before = order[:at]
         tracks = [np.asarray(planners[j].x_seq, dtype=np.float64)[:, :2] for j in before]
-        results[k] = planners[k].avoid(tracks, r[before], start)
+        results[k] = planners[k].avoid(tracks, r[before], start, max_wait=max_wait)
     return results
