@@ -15,8 +15,8 @@
 //   steps      cum by the pointer doubling of retain.hpp (k_retain_init / k_retain_double with root 0 and no ok table)
 //   check      one wavefront per node, rows in order up to the first failing one, the lanes split the hull x disc sweep; a goal
 //              hit then waits at its last row while the discs move on
-//   propagate  first down the parent chains by pointer doubling, ceil(log2 N) double-buffered rounds, joined by minimum with
-//              -1 as +infinity
+//   propagate  first down the parent chains by pointer doubling (k_clear_init<ClearLink> / k_clear_double<ClearLink>),
+//              ceil(log2 N) double-buffered rounds, joined by minimum with -1 as +infinity
 //   select     thread per node: counters, and best lowered with a global 64-bit atomic min
 //
 // The disc table [L][D][4] holds per instant and disc what upload_geometry derives for a static circle -- centre x, y | exact
@@ -32,8 +32,14 @@ template <class S> struct has_discs<S, std::enable_if_t<S::DISCS>> : std::true_t
 
 // One node of the propagate rounds: `jump` is an ancestor (the root: itself), `first` the smallest failing time index over the
 // nodes from this one up to AND INCLUDING `jump`, or -1.  (Inclusive, unlike RetainLink: the root's own row counts, and a chain
-// of 2^k nodes reaches the root in its last round.)
-struct alignas(8) ClearLink { int jump, first; };
+// of 2^k nodes reaches the root in its last round.)  A link type names the field it carries (Val, FIELD) and how two are joined: an
+// idempotent join, so that the root (jump == itself) is the identity.  Here: the minimum with -1 as +infinity.
+struct alignas(8) ClearLink {
+    typedef int Val;
+    int jump, first;
+    static constexpr int ClearLink::* FIELD = &ClearLink::first;
+    __device__ static int join(int a, int b) { return a < 0 ? b : (b < 0 ? a : (a < b ? a : b)); }
+};
 
 // counters of one call (device -> host in one copy)
 struct ClearOut {
@@ -43,7 +49,27 @@ struct ClearOut {
 
 constexpr int CLEAR_BLOCK = 256;
 
-__device__ __forceinline__ int clear_min(int a, int b) { return a < 0 ? b : (b < 0 ? a : (a < b ? a : b)); }
+// What the two checks (this one and clear_wait.hpp's) share.  The hull points into LDS by `stride` threads, of which this is
+// `tid`; the caller's __syncthreads() follows.
+__device__ __forceinline__ void clear_stage_hull(const Geo& g, double* hull_lds, int tid, int stride) {
+    for (int q = tid; q < 2 * g.V; q += stride) hull_lds[q] = g.vps[q];
+}
+// gd (the caller's copy of g) and gl for a test in which the D discs of one instant (gl.oc, set per row) are the whole world
+__device__ __forceinline__ void clear_disc_world(const Geo& g, double* hull_lds, int D, Geo& gd, GeoL& gl) {
+    gd.og = nullptr; gd.O = D;
+    gl.vps = hull_lds; gl.V = g.V; gl.O = D;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gl.bb[k] = g.hbb[k];
+}
+// row k of an edge
+template <class S>
+__device__ __forceinline__ void clear_load_row(const double* xe, const double* ue, int k, double* x, double* u, double* trig) {
+#pragma unroll
+    for (int d = 0; d < S::N; ++d) x[d] = xe[(size_t)k * S::N + d];
+#pragma unroll
+    for (int j = 0; j < S::M; ++j) u[j] = ue[(size_t)k * S::M + j];
+    trig_of<S>(x, trig);
+}
 
 // check: block i <-> node i.  `link` holds the finished step sums (RetainLink::steps = cum - elen[0]).
 template <class S>
@@ -52,14 +78,11 @@ __device__ __forceinline__ void clear_check_body(const Params& P, const Geo& g, 
                                                  int start, int* __restrict__ own, int* __restrict__ dwell, double* hull_lds, int i) {
     const int lane = threadIdx.x;
     if (i >= N) return;
-    for (int q = lane; q < 2 * g.V; q += 64) hull_lds[q] = g.vps[q];
+    clear_stage_hull(g, hull_lds, lane, 64);
     __syncthreads();
-    Geo gd = g;                                                  // the discs are the whole world of this test
-    gd.og = nullptr; gd.O = D;
+    Geo gd = g;
     GeoL gl;
-    gl.vps = hull_lds; gl.V = g.V; gl.O = D;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) gl.bb[k] = g.hbb[k];
+    clear_disc_world(g, hull_lds, D, gd, gl);
     const int len = tv.elen[i];
     const double* xe = tv.xedge + (size_t)i * tv.H * S::N;
     const double* ue = tv.uedge + (size_t)i * tv.H * S::M;
@@ -69,33 +92,18 @@ __device__ __forceinline__ void clear_check_body(const Params& P, const Geo& g, 
     int first = -1;
     double x[S::N], u[S::M], trig[2 * S::NW + 1];
     for (int k = k0; k < len && first < 0; ++k) {
-#pragma unroll
-        for (int d = 0; d < S::N; ++d) x[d] = xe[(size_t)k * S::N + d];
-#pragma unroll
-        for (int j = 0; j < S::M; ++j) u[j] = ue[(size_t)k * S::M + j];
-        trig_of<S>(x, trig);
+        clear_load_row<S>(xe, ue, k, x, u, trig);
         const int tau = base + k;
         gl.oc = table + (size_t)(tau < L - 1 ? tau : L - 1) * D * 4;
         if (!S::feasible(P.p, gd, gl, x, u, trig, lane)) first = tau;
     }
     // a goal hit waits at its last row (x, u, trig hold it when no row failed; when one did, the hit is not clear anyway, but
     // dwell is defined on the last row all the same: load it again)
-    bool in = i > 0;
-#pragma unroll
-    for (int d = 0; d < S::N; ++d) {
-        const double s = tv.state[(size_t)d * tv.cap + i];
-        in = in && (r.goal_lo[d] < s) && (s < r.goal_hi[d]);     // planner.py:442-447, as retain_goal_body
-    }
+    const bool in = goal_hit<S>(tv, r, i) && i > 0;             // (the root is no hit; its state is read all the same, as ever)
     int dw = -2;
     if (in) {
         dw = -1;
-        if (first >= 0) {
-#pragma unroll
-            for (int d = 0; d < S::N; ++d) x[d] = xe[(size_t)(len - 1) * S::N + d];
-#pragma unroll
-            for (int j = 0; j < S::M; ++j) u[j] = ue[(size_t)(len - 1) * S::M + j];
-            trig_of<S>(x, trig);
-        }
+        if (first >= 0) clear_load_row<S>(xe, ue, len - 1, x, u, trig);
         for (int tau = base + len; tau <= L - 1 && dw < 0; ++tau) {      // (base + len - 1 = start + cum[i] - 1: the arrival)
             gl.oc = table + (size_t)tau * D * 4;
             if (!S::feasible(P.p, gd, gl, x, u, trig, lane)) dw = tau;
@@ -112,28 +120,26 @@ __global__ __launch_bounds__(64) void k_clear_check(Params P, Geo g, TreeView tv
 }
 
 // links of round 0: a node and its parent
-__device__ __forceinline__ void clear_init_body(const TreeView& tv, int N, const int* __restrict__ own, ClearLink* __restrict__ a, int i) {
+template <class Link>
+__global__ void k_clear_init(TreeView tv, int N, const typename Link::Val* __restrict__ own, Link* __restrict__ a) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= N) return;
-    ClearLink l;
-    if (i == 0) { l.jump = 0; l.first = own[0]; }
-    else { l.jump = tv.pID[i]; l.first = clear_min(own[i], own[l.jump]); }
+    Link l{};
+    if (i == 0) { l.jump = 0; l.*Link::FIELD = own[0]; }
+    else { l.jump = tv.pID[i]; l.*Link::FIELD = Link::join(own[i], own[l.jump]); }
     a[i] = l;
 }
-__global__ void k_clear_init(TreeView tv, int N, const int* __restrict__ own, ClearLink* __restrict__ a) {
-    clear_init_body(tv, N, own, a, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
 
-// one doubling round: b[i] = a[i] joined with a[a[i].jump].  The minimum is idempotent: the root (jump == itself) is the identity.
-__device__ __forceinline__ void clear_double_body(int N, const ClearLink* __restrict__ a, ClearLink* __restrict__ b, int i) {
+// one doubling round: b[i] = a[i] joined with a[a[i].jump]
+template <class Link>
+__global__ void k_clear_double(int N, const Link* __restrict__ a, Link* __restrict__ b) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= N) return;
-    ClearLink l = a[i];
-    const ClearLink up = a[l.jump];
-    l.first = clear_min(l.first, up.first);
+    Link l = a[i];
+    const Link up = a[l.jump];
+    l.*Link::FIELD = Link::join(l.*Link::FIELD, up.*Link::FIELD);
     l.jump = up.jump;
     b[i] = l;
-}
-__global__ void k_clear_double(int N, const ClearLink* __restrict__ a, ClearLink* __restrict__ b) {
-    clear_double_body(N, a, b, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // select: thread per node.  first_out[i] = the finished first; the counters go through the workgroup's LDS, best through a

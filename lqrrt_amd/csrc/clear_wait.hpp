@@ -19,8 +19,8 @@
 //   steps      cum by the pointer doubling of retain.hpp, exactly as clear.hpp's
 //   check      one workgroup of four wavefronts per node; wavefront q owns the delays w = q, q + 4, ...  and writes one partial
 //              mask, joined through LDS
-//   propagate  16-byte links {jump, mask} joined by AND, inclusive of the jump target as ClearLink, ceil(log2 N) double-buffered
-//              rounds
+//   propagate  clear.hpp's k_clear_init / k_clear_double on 16-byte links {jump, mask} joined by AND, ceil(log2 N)
+//              double-buffered rounds
 //   select     thread per node: m = clear & dwell_ok, w = ctz(m); counters through LDS, best by a global 64-bit atomic min on
 //              ((w + cum) << 32 | id)
 //
@@ -33,8 +33,14 @@
 //       fourth) and each stops at its first failure; with t* the latest failure, dwell_ok is the delays with
 //       start + w + cum[i] > t*
 
-// One node of the propagate rounds: `mask` is the AND of own_ok over the nodes from this one up to AND INCLUDING `jump`.
-struct alignas(16) ClearWaitLink { int jump, pad; unsigned long long mask; };
+// One node of the propagate rounds, as ClearLink: `mask` is the AND of own_ok over the nodes from this one up to and including `jump`.
+struct alignas(16) ClearWaitLink {
+    typedef unsigned long long Val;
+    int jump, pad;
+    unsigned long long mask;
+    static constexpr unsigned long long ClearWaitLink::* FIELD = &ClearWaitLink::mask;
+    __device__ static unsigned long long join(unsigned long long a, unsigned long long b) { return a & b; }
+};
 
 // counters of one call (device -> host in one copy)
 struct ClearWaitOut {
@@ -58,14 +64,11 @@ __device__ __forceinline__ void clear_wait_check_body(const Params& P, const Geo
     __shared__ int fail[CLEAR_WAIT_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;  // (every wavefront's control flow below is uniform)
     if (i >= N) return;
-    for (int v = tid; v < 2 * g.V; v += CLEAR_WAIT_BLOCK) hull_lds[v] = g.vps[v];
+    clear_stage_hull(g, hull_lds, tid, CLEAR_WAIT_BLOCK);
     __syncthreads();
-    Geo gd = g;                                                  // the discs are the whole world of this test
-    gd.og = nullptr; gd.O = D;
+    Geo gd = g;
     GeoL gl;
-    gl.vps = hull_lds; gl.V = g.V; gl.O = D;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) gl.bb[k] = g.hbb[k];
+    clear_disc_world(g, hull_lds, D, gd, gl);
     const unsigned long long all = clear_wait_all(W);
     const unsigned long long mine = (0x1111111111111111ull << q) & all;     // the delays of this wavefront
     const int len = tv.elen[i];
@@ -73,13 +76,7 @@ __device__ __forceinline__ void clear_wait_check_body(const Params& P, const Geo
     const double* ue = tv.uedge + (size_t)i * tv.H * S::M;
     const double* last = table + (size_t)(L - 1) * D * 4;
     double x[S::N], u[S::M], trig[2 * S::NW + 1];
-    auto load = [&](int k) {
-#pragma unroll
-        for (int d = 0; d < S::N; ++d) x[d] = xe[(size_t)k * S::N + d];
-#pragma unroll
-        for (int j = 0; j < S::M; ++j) u[j] = ue[(size_t)k * S::M + j];
-        trig_of<S>(x, trig);
-    };
+    auto load = [&](int k) { clear_load_row<S>(xe, ue, k, x, u, trig); };
     // time index of row 0 at delay 0 (the root: of its last row, the only one it has as a seed)
     const int base = i == 0 ? start : start + link[tv.pID[i]].steps + tv.elen[0];
     unsigned long long alive = mine;
@@ -112,12 +109,7 @@ __device__ __forceinline__ void clear_wait_check_body(const Params& P, const Geo
         }
     }
     // a goal hit waits at its last row: (c)
-    bool in = i > 0;
-#pragma unroll
-    for (int d = 0; d < S::N; ++d) {
-        const double s = tv.state[(size_t)d * tv.cap + i];
-        in = in && (r.goal_lo[d] < s) && (s < r.goal_hi[d]);     // planner.py:442-447, as retain_goal_body
-    }
+    const bool in = goal_hit<S>(tv, r, i) && i > 0;             // (the root is no hit; its state is read all the same, as ever)
     const int arrive = base + len;                               // start + cum[i]: the first instant of the wait at delay 0
     int tstar = -1;
     if (in) {
@@ -155,33 +147,6 @@ __global__ __launch_bounds__(CLEAR_WAIT_BLOCK) void k_clear_wait_check(Params P,
     extern __shared__ double hull_lds[];
     if constexpr (has_discs<S>::value)
         clear_wait_check_body<S>(P, g, tv, r, N, link, table, L, D, start, W, own_ok, dwell_ok, hit, hull_lds, (int)blockIdx.x);
-}
-
-// links of round 0: a node and its parent
-__device__ __forceinline__ void clear_wait_init_body(const TreeView& tv, int N, const unsigned long long* __restrict__ own_ok,
-                                                     ClearWaitLink* __restrict__ a, int i) {
-    if (i >= N) return;
-    ClearWaitLink l;
-    l.pad = 0;
-    if (i == 0) { l.jump = 0; l.mask = own_ok[0]; }
-    else { l.jump = tv.pID[i]; l.mask = own_ok[i] & own_ok[l.jump]; }
-    a[i] = l;
-}
-__global__ void k_clear_wait_init(TreeView tv, int N, const unsigned long long* __restrict__ own_ok, ClearWaitLink* __restrict__ a) {
-    clear_wait_init_body(tv, N, own_ok, a, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-
-// one doubling round: b[i] = a[i] joined with a[a[i].jump].  AND is idempotent: the root (jump == itself) is the identity.
-__device__ __forceinline__ void clear_wait_double_body(int N, const ClearWaitLink* __restrict__ a, ClearWaitLink* __restrict__ b, int i) {
-    if (i >= N) return;
-    ClearWaitLink l = a[i];
-    const ClearWaitLink up = a[l.jump];
-    l.mask &= up.mask;
-    l.jump = up.jump;
-    b[i] = l;
-}
-__global__ void k_clear_wait_double(int N, const ClearWaitLink* __restrict__ a, ClearWaitLink* __restrict__ b) {
-    clear_wait_double_body(N, a, b, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // select: thread per node.  clear_out[i] = the finished mask; the counters go through the workgroup's LDS, best through a global

@@ -26,13 +26,10 @@ static int connect_check(lqrrt_engine* e, int tries, int horizon) {
 // room for `ints` ints behind the head of 8
 static int connect_scratch(lqrrt_engine* e, size_t ints) {
     if (e->d_con && ints <= e->con_cap) return 0;
-    const size_t keep = g_dalloc_bytes;
     if (e->d_con) (void)hipFree(e->d_con);
     e->d_con = nullptr; e->con_cap = 0;
     const size_t want = (ints + 1023) / 1024 * 1024;
-    const int rc = dalloc(&e->d_con, want + 8);
-    g_dalloc_bytes = keep;                                      // (allocated on first use: not part of the footprint)
-    if (rc) return rc;
+    TRY(dalloc_transient(&e->d_con, want + 8));                 // (allocated on first use: not part of the footprint)
     e->con_cap = want;
     return 0;
 }

@@ -98,6 +98,15 @@ static int dalloc(T** p, size_t count) {
     return 0;
 }
 
+// dalloc for memory that is no part of an engine's footprint: the counter stays as it was
+template <class T>
+static int dalloc_transient(T** p, size_t count) {
+    const size_t keep = g_dalloc_bytes;
+    const int rc = dalloc(p, count);
+    g_dalloc_bytes = keep;
+    return rc;
+}
+
 static NodeView tree_view(const lqrrt_engine* e, bool use_ignore) {
     NodeView v;
     v.x = e->tv.state; v.trig = e->tv.trig;

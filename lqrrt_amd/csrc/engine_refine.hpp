@@ -99,13 +99,10 @@ static int refine_prepare(lqrrt_engine* e, const int32_t* plan, int P, int tries
                           hipStream_t st, StreamDrain& drain) {
     TRY(refine_check(e, plan, P, tries, horizon, buf));
     if (P > e->ref_cap) {
-        const size_t keep = g_dalloc_bytes;
         if (e->d_ref) (void)hipFree(e->d_ref);
         e->ref_cap = 0;
-        int rc = dalloc(&e->d_ref, (size_t)2 * P);
-        if (!rc && !e->d_ref_key) rc = dalloc(&e->d_ref_key, (size_t)4);
-        g_dalloc_bytes = keep;                                  // (a few kB, allocated on first use: not part of the footprint)
-        if (rc) return rc;
+        TRY(dalloc_transient(&e->d_ref, (size_t)2 * P));        // (a few kB, allocated on first use: not part of the footprint)
+        if (!e->d_ref_key) TRY(dalloc_transient(&e->d_ref_key, (size_t)4));
         e->ref_cap = P;
     }
     drain.arm();
@@ -229,10 +226,10 @@ struct MultiChunk {
     int* lens_of(char* image, size_t q) const { return (int*)(image + o_lens) + lens_at[q]; }
 };
 
-// offsets into an image, each part 16-byte aligned
+// offsets into an image, each part aligned (16 bytes unless the owner says otherwise)
 struct Carve {
-    size_t off = 0;
-    size_t operator()(size_t bytes) { const size_t at = off; off += (bytes + 15) / 16 * 16; return at; }
+    size_t off = 0, align = 16;
+    size_t operator()(size_t bytes) { const size_t at = off; off += (bytes + align - 1) / align * align; return at; }
 };
 
 // Cuts a call into chunks: groups[k] 64-thread workgroups for engine k (0: the engine takes part in no launch; a commit asks for

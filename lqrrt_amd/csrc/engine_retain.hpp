@@ -40,6 +40,23 @@ static void retain_adopt(lqrrt_engine* e, int N, const RetainOut& h, const std::
     out->root_feasible = h.root_feasible; out->goal_hits = h.hits; out->best_end = e->best_end; out->best_steps = e->best_steps;
 }
 
+// ceil(log2 N) double-buffered rounds of a pointer-doubling kernel: 2^rounds >= N covers every parent chain.  `a` ends up as the
+// finished links, `b` as the spare.
+template <class Link>
+static void double_rounds(void (*round)(int, const Link*, Link*), int N, Link*& a, Link*& b, hipStream_t st) {
+    for (int r = 0; (1ll << r) < (long long)N; ++r) {
+        hipLaunchKernelGGL(round, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, (const Link*)a, b);
+        std::swap(a, b);
+    }
+}
+
+// The RetainLink of every node against `root` in d_a (ok == nullptr: every edge passes).  With root 0 and no ok table
+// RetainLink::steps is cum - elen[0]: the step sums of the clearance calls (engine_clear.hpp).
+static void retain_links(const lqrrt_engine* e, int root, int N, const unsigned char* ok, RetainLink*& d_a, RetainLink*& d_b, hipStream_t st) {
+    hipLaunchKernelGGL(k_retain_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, e->tv, root, N, ok, d_a);
+    double_rounds(k_retain_double, N, d_a, d_b, st);
+}
+
 static int retain_run(lqrrt_engine* e, int root, int revalidate, lqrrt_retain_stats* out, int32_t* old_to_new, hipStream_t st,
                       RetainScratch& sc) {
     const int N = e->N, n = e->n, m = e->m, H = e->H;
@@ -53,10 +70,7 @@ static int retain_run(lqrrt_engine* e, int root, int revalidate, lqrrt_retain_st
     const size_t o_local = carve(sizeof(int) * N), o_sums = carve(sizeof(int) * nblocks), o_newid = carve(sizeof(int) * N);
     const size_t o_nelen = carve(sizeof(int) * N), o_npid = carve(sizeof(int) * N), o_nsteps = carve(sizeof(int) * N);
     const size_t o_ign = carve(sizeof(unsigned long long) * words), o_out = carve(sizeof(RetainOut));
-    const size_t keep_bytes = g_dalloc_bytes;
-    int rc = dalloc(&sc.small, off);
-    g_dalloc_bytes = keep_bytes;                                // (transient: not part of the engine's footprint)
-    if (rc) return rc;
+    TRY(dalloc_transient(&sc.small, off));                      // (transient: not part of the engine's footprint)
     RetainLink* d_a = (RetainLink*)(sc.small + o_a);
     RetainLink* d_b = (RetainLink*)(sc.small + o_b);
     unsigned char* d_ok = (unsigned char*)(sc.small + o_ok);
@@ -83,14 +97,8 @@ static int retain_run(lqrrt_engine* e, int root, int revalidate, lqrrt_retain_st
                                        root, N, d_ok, d_out));
         HIPCHK(hipGetLastError());
     }
-    // ---- propagate: 2^rounds >= N covers every parent chain
-    hipLaunchKernelGGL(k_retain_init, per_node, t256, 0, st, e->tv, root, N, revalidate ? d_ok : (const unsigned char*)nullptr, d_a);
-    int rounds = 0;
-    while ((1ll << rounds) < (long long)N) ++rounds;
-    for (int r = 0; r < rounds; ++r) {
-        hipLaunchKernelGGL(k_retain_double, per_node, t256, 0, st, N, (const RetainLink*)d_a, d_b);
-        std::swap(d_a, d_b);
-    }
+    // ---- propagate
+    retain_links(e, root, N, revalidate ? d_ok : (const unsigned char*)nullptr, d_a, d_b, st);
     // ---- scan
     hipLaunchKernelGGL(k_retain_flags, dim3((unsigned)nblocks), dim3(RETAIN_BLOCK), 0, st, root, N, (const RetainLink*)d_a,
                        revalidate ? d_ok : (const unsigned char*)nullptr, d_keep, d_local, d_sums, d_out);
@@ -109,9 +117,7 @@ static int retain_run(lqrrt_engine* e, int root, int revalidate, lqrrt_retain_st
     std::vector<int> h_npid, h_nelen;
     if (kept < N) {
         const size_t widest = std::max((size_t)H * std::max(n, m), (size_t)m * n);
-        rc = dalloc(&sc.big, (size_t)kept * widest);
-        g_dalloc_bytes = keep_bytes;
-        if (rc) return rc;
+        TRY(dalloc_transient(&sc.big, (size_t)kept * widest));
         h_npid.resize((size_t)kept); h_nelen.resize((size_t)kept);
         HIPCHK(hipMemcpyAsync(h_npid.data(), d_npid, sizeof(int) * kept, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h_nelen.data(), d_nelen, sizeof(int) * kept, hipMemcpyDeviceToHost, st));
@@ -237,10 +243,7 @@ static int retain_multi_chunk(lqrrt_engine** eng, int n, const int32_t* roots, c
     const size_t o_nelen = carve(sizeof(int) * sumN), o_npid = carve(sizeof(int) * sumN), o_nsteps = carve(sizeof(int) * sumN);
     const size_t o_ign = carve(sizeof(unsigned long long) * sumW), o_out = carve(sizeof(RetainOut) * n), o_desc = carve(sizeof(RetainDesc) * n);
     RetainMultiScratch sc;
-    const size_t keep_bytes = g_dalloc_bytes;
-    int rc = dalloc(&sc.small, off);
-    g_dalloc_bytes = keep_bytes;                                // (transient: not part of any engine's footprint)
-    if (rc) return rc;
+    TRY(dalloc_transient(&sc.small, off));                      // (transient: not part of any engine's footprint)
     RetainOut* d_out = (RetainOut*)(sc.small + o_out);
     RetainDesc* d_desc = (RetainDesc*)(sc.small + o_desc);
     int* d_newid = (int*)(sc.small + o_newid);
@@ -313,11 +316,7 @@ static int retain_multi_chunk(lqrrt_engine** eng, int n, const int32_t* roots, c
 
     // ---- move (nothing of any tree has been written so far).  An engine that keeps every node moves nothing.
     const size_t widest = std::max(std::max((size_t)H * std::max(ns, m), (size_t)m * ns), (size_t)std::max(ns, 2 * nw));
-    if (any_moves) {
-        rc = dalloc(&sc.big, sum_kept * widest);
-        g_dalloc_bytes = keep_bytes;
-        if (rc) return rc;
-    }
+    if (any_moves) TRY(dalloc_transient(&sc.big, sum_kept * widest));
     std::vector<RetainDesc> hd2(hd);                           // (a second staging copy: the first upload may still read `hd`)
     std::vector<long long> c_old((size_t)n), c_oldb((size_t)n), c_new((size_t)n), c_newb((size_t)n), c_small((size_t)n), c_goal((size_t)n);
     {

@@ -153,11 +153,9 @@ extern "C" int lqrrt_tree_get_edges_of(lqrrt_engine* e, const int32_t* ids, int 
     TRY(use_device(e));
     const size_t xn = (size_t)count * e->H * e->n, un = (size_t)count * e->H * e->m;
     double* d_x = nullptr; double* d_u = nullptr; int* d_ids = nullptr;
-    const size_t keep = g_dalloc_bytes;
-    int rc = dalloc(&d_x, xn);
-    if (!rc) rc = dalloc(&d_u, un);
-    if (!rc) rc = dalloc(&d_ids, (size_t)count);
-    g_dalloc_bytes = keep;                                   // (transient: not part of the engine's footprint)
+    int rc = dalloc_transient(&d_x, xn);                     // (transient: not part of the engine's footprint)
+    if (!rc) rc = dalloc_transient(&d_u, un);
+    if (!rc) rc = dalloc_transient(&d_ids, (size_t)count);
     if (!rc && hipMemcpy(d_ids, ids, sizeof(int) * count, hipMemcpyHostToDevice) != hipSuccess) rc = fail(LQRRT_E_HIP, "hipMemcpy failed");
     if (!rc) {
         hipLaunchKernelGGL(k_gather_edges, dim3(count), dim3(128), 0, nullptr, e->tv, d_ids, count, e->n, e->m, d_x, d_u);

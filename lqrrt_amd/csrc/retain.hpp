@@ -252,19 +252,24 @@ __global__ void k_retain_root_edge(TreeView tv, int n, int m) {
     retain_root_edge_body(tv, n, m);
 }
 
+// node i lies strictly inside the goal box (planner.py:442-447)
+template <class S>
+__device__ __forceinline__ bool goal_hit(const TreeView& tv, const Res& r, int i) {
+    bool in = true;
+#pragma unroll
+    for (int d = 0; d < S::N; ++d) {
+        const double x = tv.state[(size_t)d * tv.cap + i];
+        in = in && (r.goal_lo[d] < x) && (x < r.goal_hi[d]);
+    }
+    return in;
+}
+
 // goal: thread per kept non-root node of the NEW tree.  ign: a zeroed bitmap of the new tree.
 template <class S>
 __device__ __forceinline__ void retain_goal_body(const TreeView& tv, const Res& r, int kept, const int* __restrict__ npid,
                                                  const int* __restrict__ nsteps, unsigned long long* __restrict__ ign,
                                                  RetainOut* __restrict__ out, int k) {
-    if (k >= kept) return;
-    bool in = true;
-#pragma unroll
-    for (int d = 0; d < S::N; ++d) {
-        const double x = tv.state[(size_t)d * tv.cap + k];
-        in = in && (r.goal_lo[d] < x) && (x < r.goal_hi[d]);     // planner.py:442-447
-    }
-    if (!in) return;
+    if (k >= kept || !goal_hit<S>(tv, r, k)) return;
     atomicAdd(&out->hits, 1);
     atomicMin(&out->best, ((unsigned long long)(unsigned)nsteps[k] << 32) | (unsigned long long)(unsigned)k);
     // the hit's root path joins the ignore set (planner.py:270).  A climber may stop at a bit that is already set: whoever

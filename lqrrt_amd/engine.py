@@ -281,18 +281,7 @@ class Engine(object):
         best_steps), and with `per_node` also first [N] and dwell_first [N] (int32: the time index of the first conflict on a
         node's root path, -1 = clear; for a goal hit the first conflict while it waits at the goal, -1 = none, -2 = not a hit).
         Reads only: tree, goal bookkeeping and footprint stay as they are."""
-        table, r, start = self.track_table(tracks, radii, start)
-        st = nat.ClearStats()
-        first = dwell = None
-        if per_node:
-            n = max(self.size, 1)
-            first, dwell = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
-        nat.check(nat.lib().lqrrt_tree_clear(self.h, nat.ptr(table), nat.ptr(r), table.shape[0], table.shape[1], start, C.byref(st),
-                                             None if first is None else nat.ptr(first), None if dwell is None else nat.ptr(dwell),
-                                             self._stream()))
-        if per_node:
-            return st.as_dict(), first[:st.size], dwell[:st.size]
-        return st.as_dict()
+        return self._clear("lqrrt_tree_clear", nat.ClearStats, np.int32, tracks, radii, start, None, per_node)
 
     @staticmethod
     def wait_count(waits, what="waits", lo=1, hi=64):
@@ -310,18 +299,22 @@ class Engine(object):
         `per_node` also clear [N] and dwell_ok [N] (uint64: bit w of clear = the node's root path and the wait before it are clear
         at delay w; bit w of dwell_ok = a goal hit can wait at the goal from its arrival at delay w on, 0 for a node that is no
         hit).  Reads only: tree, goal bookkeeping and footprint stay as they are."""
+        return self._clear("lqrrt_tree_clear_wait", nat.ClearWaitStats, np.uint64, tracks, radii, start, waits, per_node)
+
+    def _clear(self, call, stats, dtype, tracks, radii, start, waits, per_node):
+        """tree_clear (`waits` None) and tree_clear_wait: the arguments checked in their order, the counters, and with `per_node`
+        the call's two arrays [N] of `dtype`."""
         table, r, start = self.track_table(tracks, radii, start)
-        waits = self.wait_count(waits)
-        st = nat.ClearWaitStats()
-        clear = dwell = None
+        extra = () if waits is None else (self.wait_count(waits),)
+        st = stats()
+        a = b = None
         if per_node:
             n = max(self.size, 1)
-            clear, dwell = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
-        nat.check(nat.lib().lqrrt_tree_clear_wait(self.h, nat.ptr(table), nat.ptr(r), table.shape[0], table.shape[1], start, waits,
-                                                  C.byref(st), None if clear is None else nat.ptr(clear),
-                                                  None if dwell is None else nat.ptr(dwell), self._stream()))
+            a, b = np.empty(n, dtype=dtype), np.empty(n, dtype=dtype)
+        nat.check(getattr(nat.lib(), call)(self.h, nat.ptr(table), nat.ptr(r), table.shape[0], table.shape[1], start, *extra, C.byref(st),
+                                           None if a is None else nat.ptr(a), None if b is None else nat.ptr(b), self._stream()))
         if per_node:
-            return st.as_dict(), clear[:st.size], dwell[:st.size]
+            return st.as_dict(), a[:st.size], b[:st.size]
         return st.as_dict()
 
     def tree_truncate(self, size):

@@ -17,6 +17,7 @@ import lqrrt_amd
 from lqrrt_amd import _native as nat
 from lqrrt_amd.engine import Engine
 import clear_reference as cl
+from clear_common import FORBIDDEN, clear_host_text
 import feasibility_reference as fr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -307,24 +308,46 @@ def test_clear_stays_plain_launches():
     csrc = os.path.join(ROOT, "lqrrt_amd", "csrc")
     for f in ("clear.hpp", "engine_clear.hpp"):
         text = open(os.path.join(csrc, f)).read()
-        for word in ("hipLaunchCooperativeKernel", "hipModuleLaunchCooperativeKernel", "cooperative_groups", "grid.sync", "this_grid",
-                     "asm(", "asm volatile", "__threadfence"):
+        for word in FORBIDDEN:
             assert word not in text, (f, word)
     src = open(os.path.join(csrc, "clear.hpp")).read()
     assert src.count("__launch_bounds__(64)") == 1 and "S::feasible(" in src and "trig_of<S>(" in src and "= stage_geo(" not in src
     assert "hull_lds[q] = g.vps[q]" in src and "gd.og = nullptr; gd.O = D;" in src and "has_discs" in src
-    host = open(os.path.join(csrc, "engine_clear.hpp")).read()
-    assert "k_retain_init" in host and "k_retain_double" in host and "k_clear_check<S>" in host and "hull_bytes, st" in host
+    host, parts = clear_host_text()
+    retain = open(os.path.join(csrc, "engine_retain.hpp")).read()
+    links = retain[retain.index("static void retain_links("):retain.index("static int retain_run(")]
+    rounds = retain[retain.index("static void double_rounds("):retain.index("static void retain_links(")]
+    assert "k_retain_init" in links and "double_rounds(k_retain_double" in links and "hipLaunchKernelGGL(round," in rounds
+    assert "retain_links(e, 0, N, nullptr" in parts["run"] and "k_clear_check<S>" in host and "hull_bytes, st" in host
     # every refusal stands before the first thing that is enqueued or allocated
-    first_work = min(host.index(w) for w in ("dalloc(", "hipMemcpyAsync(", "hipLaunchKernelGGL("))
     for refusal in ("L < 1 || D < 1", "start < 0", "std::isfinite(", "radii_host[d] >= 0.0", "!e->has_goal", "leave 31 bits", "has_discs<S>::value",
-                    "hull_bytes > e->lds_limit"):
-        assert 0 <= host.index(refusal) < first_work, refusal
-    assert "g_dalloc_bytes = keep_bytes" in host                                   # transient: the footprint stays
+                    "hull_bytes + C::CHECK_LDS > e->lds_limit"):
+        assert 0 <= parts["check"].index(refusal), refusal
+    order = [parts["check"].index(r) for r in ("null argument", "L < 1 || D < 1", "start < 0", "track table too large", "std::isfinite(",
+                                               "radii_host[d] >= 0.0", "waits < 1 || waits > 64", "has_discs<S>::value", "!e->has_res",
+                                               "!e->has_goal", "the root's edge has no row", "p < 0 || p >= v", "leave 31 bits",
+                                               "> e->lds_limit")]
+    assert order == sorted(order)                                                  # ... in the order the calls have always refused in
+    assert "static constexpr size_t CHECK_LDS = 0" in host and 'WAIT_TERM = "";' in host
+    # transient: the footprint stays
+    assert "dalloc_transient(&sc.mem" in parts["run"] and "dalloc(" not in host
+    launch = open(os.path.join(csrc, "engine_launch.hpp")).read()
+    transient = launch[launch.index("static int dalloc_transient("):]
+    transient = transient[:transient.index("\n}\n")]
+    assert transient.index("keep = g_dalloc_bytes") < transient.index("dalloc(p, count)") < transient.index("g_dalloc_bytes = keep;")
     systems = open(os.path.join(csrc, "systems.hpp")).read()
     assert systems.count("static constexpr bool DISCS = true;") == 2               # BoatCommon (the boats) and Car
     kernels = open(os.path.join(csrc, "kernels.hpp")).read()
     assert kernels.index('#include "retain.hpp"') < kernels.index('#include "clear.hpp"')
+    engine = open(os.path.join(csrc, "engine.hip")).read()
+    assert engine.index('#include "engine_retain.hpp"') < engine.index('#include "engine_refine.hpp"') < engine.index('#include "engine_clear.hpp"')
+
+
+def test_the_two_signatures_are_what_they_were():
+    import ctypes as C
+    I, P = C.c_int, C.c_void_p
+    assert nat.SIGNATURES["lqrrt_tree_clear"] == (I, [P, P, P, I, I, I, C.POINTER(nat.ClearStats), P, P, P])
+    assert nat.SIGNATURES["lqrrt_tree_clear_wait"] == (I, [P, P, P, I, I, I, I, C.POINTER(nat.ClearWaitStats), P, P, P])
 
 
 def test_check_kernel_stays_in_the_class_of_the_retain_check():

@@ -10,22 +10,9 @@ import pytest
 import clear_reference as cl
 import feasibility_reference as fr
 import retain_reference as rr
+from clear_common import WAVE, _grown, _load
 
 pytestmark = pytest.mark.gpu
-
-WAVE = 256
-
-
-def _load(system, tree, H, capacity=None, goal=None, goal_buffer=None, dt=0.1):
-    """An engine with `tree` (state, K, pID, elen and packed edges) loaded and the goal box set."""
-    from lqrrt_amd.engine import Engine
-    eng = Engine(system, capacity=(len(tree.pID) + 64) if capacity is None else capacity, max_wave=64)
-    goal = system.goal if goal is None else goal
-    buf = system.goal_buffer if goal_buffer is None else goal_buffer
-    eng.set_resolution(dt, 0.0, H, np.ones(system.nstates), goal, np.abs(np.asarray(buf, dtype=np.float64)))
-    xe, ue = tree.packed()
-    eng.tree_load(tree.state, tree.K, tree.pID, tree.elen, xe, ue)
-    return eng
 
 
 def _compare(eng, ref, tracks, radii, start):
@@ -150,23 +137,6 @@ def test_refusals_on_the_device():
 
 
 # ------------------------------------------------------------------------------------------------ nothing is modified
-
-def _grown(seed=1, size=600):
-    """A boat_advanced tree grown on the device by an engine set up like Planner does it: resolution, default sampler, MT19937."""
-    import lqrrt_amd
-    from lqrrt_amd.engine import Engine
-    s = lqrrt_amd.systems.BoatAdvanced(0)
-    kw = s.plan_kwargs
-    eng = Engine(s, capacity=1200 + 2 * WAVE + 8, max_wave=WAVE)
-    eng.set_resolution(kw["dt"], kw["FPR"], int(kw["horizon"] / kw["dt"]), np.abs(s.error_tol), s.goal, np.abs(s.goal_buffer))
-    space = np.array(s.sample_space, dtype=np.float64)
-    eng.set_sampler(np.mean(space, axis=1), np.diff(space).flatten(), np.array(s.goal_bias, dtype=np.float64), 10)
-    st = np.random.RandomState(seed).get_state()
-    eng.set_mt19937(st[1], st[2])
-    eng.tree_reset(s.x0)
-    eng.extend(WAVE, node_limit=size)
-    return s, eng
-
 
 def test_the_tree_is_not_modified_and_grows_on_as_its_twin():
     s, eng = _grown()

@@ -17,6 +17,7 @@ import lqrrt_amd
 from lqrrt_amd import _native as nat
 from lqrrt_amd.engine import Engine
 import clear_reference as cl
+from clear_common import FORBIDDEN, clear_host_text
 import clear_wait_reference as cw
 import feasibility_reference as fr
 
@@ -209,26 +210,39 @@ def test_header_declares_the_call():
 
 
 def test_clear_wait_stays_plain_launches():
-    for f in ("clear_wait.hpp", "engine_clear_wait.hpp"):
+    for f in ("clear_wait.hpp", "engine_clear.hpp"):
         text = open(os.path.join(CSRC, f)).read()
-        for word in ("hipLaunchCooperativeKernel", "hipModuleLaunchCooperativeKernel", "cooperative_groups", "grid.sync", "this_grid",
-                     "asm(", "asm volatile", "__threadfence"):
+        for word in FORBIDDEN:
             assert word not in text, (f, word)
     src = open(os.path.join(CSRC, "clear_wait.hpp")).read()
-    assert "S::feasible(" in src and "trig_of<S>(" in src and "= stage_geo(" not in src and "has_discs<S>::value" in src
+    shared = open(os.path.join(CSRC, "clear.hpp")).read()
+    row = shared[shared.index("void clear_load_row("):]
+    assert "S::feasible(" in src and "clear_load_row<S>(" in src and "trig_of<S>(" in row[:row.index("\n}\n")]
+    assert "= stage_geo(" not in src and "has_discs<S>::value" in src
     assert "1 <<" not in src.replace("1ull <<", "") and "__builtin_ctz(" not in src and "__ffs(" not in src      # 64-bit shifts and ctz
-    host = open(os.path.join(CSRC, "engine_clear_wait.hpp")).read()
-    assert "k_retain_init" in host and "k_retain_double" in host and "k_clear_wait_check<S>" in host and "hull_bytes, st" in host
-    code = host[host.index('extern "C" int lqrrt_tree_clear_wait'):]
-    first_work = min(code.index(w) for w in ("dalloc(", "hipMemcpyAsync(", "hipLaunchKernelGGL("))
+    host, parts = clear_host_text()       # the host path of both calls: the refusals (clear_check) stand before all work (clear_run)
+    retain = open(os.path.join(CSRC, "engine_retain.hpp")).read()
+    links = retain[retain.index("static void retain_links("):retain.index("static int retain_run(")]
+    assert "k_retain_init" in links and "k_retain_double" in links and "retain_links(" in parts["run"]
+    assert "k_clear_wait_check<S>" in host and "hull_bytes, st" in host
+    code = parts["wait"]
+    assert "clear_call<ClearWait>(e, tracks_host, radii_host, L, D, start, waits," in code
     for refusal in ("L < 1 || D < 1", "start < 0", "std::isfinite(", "radii_host[d] >= 0.0", "waits < 1 || waits > 64", "has_discs<S>::value",
                     "!e->has_goal", "(long long)start + (waits - 1) + deepest > 0x7fffffffLL", "> e->lds_limit"):
-        assert 0 <= code.index(refusal) < first_work, refusal
-    assert "g_dalloc_bytes = keep_bytes" in code and "(void)hipStreamSynchronize(st)" in code
+        assert 0 <= parts["check"].index(refusal), refusal
+    assert "static constexpr size_t CHECK_LDS = 64" in host and "hull_bytes + C::CHECK_LDS > e->lds_limit" in parts["check"]
+    # transient, and the stream is drained before the scratch goes: the guard stands behind the scratch and is armed before the first copy
+    run = parts["run"]
+    assert "dalloc(" not in host and run.index("ClearScratch sc;") < run.index("dalloc_transient(&sc.mem") < run.index("StreamDrain drain(st);")
+    assert run.index("StreamDrain drain(st);") < run.index("drain.arm();") < run.index("hipMemcpyAsync(")
+    assert run.index("HIPCHK(hipStreamSynchronize(st));") < run.index("drain.disarm();")
+    refine = open(os.path.join(CSRC, "engine_refine.hpp")).read()
+    guard = refine[refine.index("struct StreamDrain {"):]
+    assert "(void)hipStreamSynchronize(st)" in guard[:guard.index("\n};\n")]
     kernels = open(os.path.join(CSRC, "kernels.hpp")).read()
     assert kernels.index('#include "clear.hpp"') < kernels.index('#include "clear_wait.hpp"')
     engine = open(os.path.join(CSRC, "engine.hip")).read()
-    assert engine.index('#include "engine_clear.hpp"') < engine.index('#include "engine_clear_wait.hpp"')
+    assert engine.index('#include "engine_refine.hpp"') < engine.index('#include "engine_clear.hpp"') and "engine_clear_wait.hpp" not in engine
 
 
 def test_check_kernel_stays_in_the_class_of_the_retain_check():
