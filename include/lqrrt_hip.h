@@ -358,6 +358,25 @@ typedef struct {
 int lqrrt_tree_clear_wait(lqrrt_engine* e, const double* tracks_host, const double* radii_host, int L, int D, int start, int waits,
                           lqrrt_clear_wait_stats* out, uint64_t* clear_host, uint64_t* dwell_host, void* stream);
 
+/* lqrrt_tree_clear and lqrrt_tree_clear_wait for n engines at once (lqrrt_amd.avoids, deconflict(batched=True): a fleet that
+ * checks its plans every tick against tracked traffic).  The rule is the one stated above (DESIGN.md sections 16 and 17),
+ * unchanged: member k's out[k] and per-node arrays are exactly what the one-tree call on engines[k] with tracks_host[k],
+ * radii_host[k], L[k], D[k], start[k] (and waits[k]) gives -- every counter, every per-node value.  first_host / dwell_host
+ * (clear_host / dwell_host) are arrays of n pointers, each [tree size of engine k]; the array or single entries may be NULL.
+ * What is shared is the work around the kernels: every stage is ONE launch whose grid spans the engines,
+ * and there is one allocation per chunk of up to 32 engines and one synchronise per call.  Members that pass the same
+ * tracks_host[k] and radii_host[k] pointers with equal L and D (the novice boats: and equal inflation) share one uploaded table.
+ * Nothing of any tree is written; all device memory of the call is transient and no engine's lqrrt_engine_footprint changes.
+ * Synchronous.  The engines share the device and the model, n <= 128, no engine appears twice, none is generic.  EVERY argument
+ * of EVERY member is checked before anything is allocated or enqueued, with the one-tree calls' codes and messages followed by
+ * "(engine k)"; a refused call writes nothing into any output. */
+int lqrrt_tree_clear_multi(lqrrt_engine** engines, int n, const double* const* tracks_host, const double* const* radii_host,
+                           const int32_t* L, const int32_t* D, const int32_t* start, lqrrt_clear_stats* out /*[n]*/,
+                           int32_t* const* first_host, int32_t* const* dwell_host, void* stream);
+int lqrrt_tree_clear_wait_multi(lqrrt_engine** engines, int n, const double* const* tracks_host, const double* const* radii_host,
+                                const int32_t* L, const int32_t* D, const int32_t* start, const int32_t* waits,
+                                lqrrt_clear_wait_stats* out /*[n]*/, uint64_t* const* clear_host, uint64_t* const* dwell_host, void* stream);
+
 /* Overwrites the ignore bits of nodes [first, first+count) (planner.py:270 `ignores`). */
 int lqrrt_tree_set_ignored(lqrrt_engine* e, int first, int count, const uint8_t* flags_host);
 

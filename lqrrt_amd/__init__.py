@@ -16,13 +16,14 @@ budget ran out before a goal hit connected to the goal through shared calls), co
 list of waypoints), fleet_goal_costs (what every planner's tree would pay to reach each of a shared list of places, one matrix
 through shared calls), retargets (every planner given a new goal from the tree it holds, through shared calls) and deconflict
 (prioritised planning over the trees as they stand: every planner picks the best plan of its tree that stays clear of the plans of
-those before it, Planner.avoid).  Importing works without a GPU; computing does not.
+those before it, Planner.avoid) and avoids (Planner.avoid for a fleet against shared or
+per-planner traffic: the trees of a group checked in one native call).  Importing works without a GPU; computing does not.
 """
 from .constraints import Constraints
-from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias, fleet_goal_costs, retargets, deconflict
+from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias, fleet_goal_costs, retargets, deconflict, avoids
 from .tree import Tree
 from . import systems
 from . import dare
 
 __all__ = ["Constraints", "Planner", "Tree", "systems", "dare", "update_plans", "refine_plans", "connect_goals", "connect_vias",
-           "fleet_goal_costs", "retargets", "deconflict"]
+           "fleet_goal_costs", "retargets", "deconflict", "avoids"]

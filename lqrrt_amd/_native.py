@@ -110,6 +110,8 @@ SIGNATURES = {
     "lqrrt_tree_retain_multi": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "lqrrt_tree_clear": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(ClearStats), _P, _P, _P]),
     "lqrrt_tree_clear_wait": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(ClearWaitStats), _P, _P, _P]),
+    "lqrrt_tree_clear_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lqrrt_tree_clear_wait_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_tree_get_edges": (_I, [_P, _I, _I, _P, _P]),
     "lqrrt_tree_mark": (_I, [_P]),
     "lqrrt_tree_rewind": (_I, [_P]),

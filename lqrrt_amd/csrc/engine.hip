@@ -87,6 +87,7 @@ static int fail(int code, const char* fmt, ...) {
 #include "engine_retain.hpp"      // ABI: tree_retain (Planner.replan)
 #include "engine_refine.hpp"      // ABI: refine_search / refine_commit (Planner.refine_plan; + _multi: retain_grid); the host path the next four share
 #include "engine_clear.hpp"       // ABI: tree_clear / tree_clear_wait (Planner.avoid: the tree's plans against moving discs, without and with max_wait)
+#include "engine_clear_multi.hpp" // ABI: tree_clear_multi / tree_clear_wait_multi (avoids, deconflict(batched): the same for several trees per launch)
 #include "engine_connect.hpp"     // ABI: connect_search / connect_commit (Planner.connect_goal: goal chains from every tree node; + _multi)
 #include "engine_reach.hpp"       // ABI: reach_search / reach_commit (Planner.goal_costs / retarget: one tree asked about many goals)
 #include "engine_reach_multi.hpp" // ABI: reach_search_multi / reach_commit_multi (fleet_goal_costs / retargets: the same for several trees)

@@ -215,6 +215,7 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "retain.hpp"     // k_retain_*                                              (Planner.replan: re-root, re-validate, compact the tree)
 #include "clear.hpp"      // k_clear_*                                                (Planner.avoid: which plans of the tree stay clear of moving discs)
 #include "clear_wait.hpp" // k_clear_wait_*                                           (Planner.avoid with max_wait: the same for up to 64 departure delays at once)
+#include "clear_multi.hpp" // k_clear_*_multi                                         (avoids / deconflict(batched): both clearance queries for several trees per launch)
 #include "refine.hpp"     // k_refine_search / k_refine_commit (+ _multi: RetainGrid) (Planner.refine_plan: shortcuts of a found plan)
 #include "connect.hpp"    // k_connect_search (+ _multi: ProtoTable, RetainGrid)      (Planner.connect_goal: goal chains from every tree node)
 #include "reach.hpp"      // k_reach_search                                           (Planner.goal_costs / retarget: those chains to MANY goals per launch)

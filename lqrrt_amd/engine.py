@@ -317,6 +317,71 @@ class Engine(object):
             return st.as_dict(), a[:st.size], b[:st.size]
         return st.as_dict()
 
+    @staticmethod
+    def tree_clear_multi(engines, tables, radii, starts, per_node=False):
+        """tree_clear for n engines in one native call (lqrrt_tree_clear_multi): every stage one kernel launch that spans the
+        engines, one allocation per chunk of 32 and one wait per call.  `tables`, `radii`, `starts`: one entry per engine, each
+        what track_table takes; engines that are handed the SAME table and radii objects (arrays, as track_table returns them)
+        share one upload.  Returns, per engine, exactly what its own tree_clear(tables[k], radii[k], starts[k], per_node) returns.
+        The engines share device and model.  Every argument of every engine is checked before anything is launched (ValueError /
+        NativeError as tree_clear, the message naming the engine); nothing of any tree is written."""
+        return Engine._clear_multi("lqrrt_tree_clear_multi", nat.ClearStats, np.int32, engines, tables, radii, starts, None, per_node)
+
+    @staticmethod
+    def tree_clear_wait_multi(engines, tables, radii, starts, waits, per_node=False):
+        """tree_clear_wait for n engines in one native call (lqrrt_tree_clear_wait_multi), as tree_clear_multi; `waits`: one count
+        for all or one per engine, each 1 .. 64.  Returns, per engine, exactly what its own tree_clear_wait returns."""
+        return Engine._clear_multi("lqrrt_tree_clear_wait_multi", nat.ClearWaitStats, np.uint64, engines, tables, radii, starts, waits,
+                                   per_node)
+
+    @staticmethod
+    def _clear_multi(call, stats, dtype, engines, tables, radii, starts, waits, per_node):
+        """tree_clear_multi (`waits` None) and tree_clear_wait_multi: every engine's arguments checked in the solo calls' order, one
+        native call, and per engine what _clear returns."""
+        engines = list(engines)
+        n = len(engines)
+        if n < 1:
+            raise ValueError("no engines")
+        tables, radii, starts = list(tables), list(radii), list(starts)
+        if not len(tables) == len(radii) == len(starts) == n:
+            raise ValueError("expected one track table, one radii array and one start per engine")
+        if waits is not None:
+            waits = [waits] * n if isinstance(waits, (int, np.integer)) else list(waits)
+            if len(waits) != n:
+                raise ValueError("expected one wait count, or one per engine")
+            waits = np.array([Engine.wait_count(w) for w in waits], dtype=np.int32)
+        # (track_table hands a contiguous float64 table back as it is: engines given one object keep one pointer)
+        seen, tabs = {}, []
+        for k in range(n):
+            key = (id(tables[k]), id(radii[k]))
+            if key not in seen:
+                seen[key] = Engine.track_table(tables[k], radii[k], 0)[:2]
+            tabs.append(seen[key])
+            if int(starts[k]) != starts[k] or int(starts[k]) < 0:
+                raise ValueError("start must be an integer >= 0.")
+        Ls =np.array([t.shape[0] for t, _ in tabs], dtype=np.int32)
+        Ds = np.array([t.shape[1] for t, _ in tabs], dtype=np.int32)
+        st0 = np.array([int(s) for s in starts], dtype=np.int64)
+        if np.any(st0 > 2 ** 31 - 1):
+            raise ValueError("start leaves 31 bits.")
+        st0 = st0.astype(np.int32)
+        handles = (C.c_void_p * n)(*[e.h for e in engines])
+        t_ptrs = (C.c_void_p * n)(*[t.ctypes.data for t, _ in tabs])
+        r_ptrs = (C.c_void_p * n)(*[r.ctypes.data for _, r in tabs])
+        out = (stats * n)()
+        a = b = a_ptrs = b_ptrs = None
+        if per_node:
+            a = [np.empty(max(e.size, 1), dtype=dtype) for e in engines]
+            b = [np.empty(max(e.size, 1), dtype=dtype) for e in engines]
+            a_ptrs = (C.c_void_p * n)(*[x.ctypes.data for x in a])
+            b_ptrs = (C.c_void_p * n)(*[x.ctypes.data for x in b])
+        extra = () if waits is None else (nat.ptr(waits),)
+        nat.check(getattr(nat.lib(), call)(handles, n, t_ptrs, r_ptrs, nat.ptr(Ls), nat.ptr(Ds), nat.ptr(st0), *extra, out, a_ptrs, b_ptrs,
+                                           engines[0]._stream()))
+        if per_node:
+            return [(out[k].as_dict(), a[k][:out[k].size], b[k][:out[k].size]) for k in range(n)]
+        return [out[k].as_dict() for k in range(n)]
+
     def tree_truncate(self, size):
         nat.check(nat.lib().lqrrt_tree_truncate(self.h, int(size)))
         self.epoch += 1

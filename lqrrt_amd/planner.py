@@ -841,22 +841,41 @@ class Planner:
                                       "cannot call it on the rows of the tree.")
         table, radii, start = Engine.track_table(tracks, radii, start)
         max_wait = Engine.wait_count(max_wait, "max_wait", 0, 63)
+        run = self._avoid_begin()
+        if run is None:
+            return None
+        if max_wait == 0:
+            out, first, dwell = self._engine.tree_clear(table, radii, start, per_node=True)
+        else:
+            out, clear, dwell_ok = self._engine.tree_clear_wait(table, radii, start, max_wait + 1, per_node=True)
+            if self._avoid_plan_holds(run, clear, dwell_ok, max_wait):
+                first = dwell = None
+            else:                                                   # the time of its first conflict: the plain query, once
+                _, first, dwell = self._engine.tree_clear(table, radii, start + self.plan_wait, per_node=True)
+        return self._avoid_end(run, out, first, dwell, start, adopt)
+
+    # The parts of avoid that it shares with avoids and deconflict(batched=True), which make the device calls for several planners
+    # at once: who takes part (_avoid_begin), whether the wait query already shows the current plan to be clear
+    # (_avoid_plan_holds), and what an answer leaves behind (_avoid_end).
+    def _avoid_begin(self):
+        """avoid's state (_RefineRun), or None when there is no tree of this planner on the device.  Reads only."""
         run = self._refine_begin(need_goal=False)
         if run is None:
             return None
         if self.goal is None or not np.array_equal(self.goal, self._grown_goal):
             raise RuntimeError("avoid: the goal changed since the tree was grown; use update_plan, replan or retarget.")
+        return run
+
+    def _avoid_plan_holds(self, run, clear, dwell_ok, max_wait):
+        """From the wait query's masks: the current plan is clear as it stands, with the wait it was adopted with."""
+        end, now = run.core[-1], self.plan_wait
+        bit = (1 << now) if now <= max_wait else 0
+        return bool(int(clear[end]) & bit and (not self.plan_reached_goal or int(dwell_ok[end]) & bit))
+
+    def _avoid_end(self, run, out, first, dwell, start, adopt):
+        """avoid's dict from the counters `out` and the plain query's per-node arrays at the current plan's departure (None: the
+        plan is clear), and the adoption of the best hit."""
         end = run.core[-1]
-        if max_wait == 0:
-            out, first, dwell = self._engine.tree_clear(table, radii, start, per_node=True)
-        else:
-            out, clear, dwell_ok = self._engine.tree_clear_wait(table, radii, start, max_wait + 1, per_node=True)
-            now = self.plan_wait                                    # the current plan leaves after the wait it was adopted with
-            bit = (1 << now) if now <= max_wait else 0
-            if int(clear[end]) & bit and (not self.plan_reached_goal or int(dwell_ok[end]) & bit):
-                first = dwell = None
-            else:                                                   # the time of its first conflict: the plain query, once
-                _, first, dwell = self._engine.tree_clear(table, radii, start + now, per_node=True)
         if first is None:
             out["plan_first"] = None
         else:
@@ -1485,7 +1504,7 @@ def retargets(planners, goals, goal_tries=8, nodes=None, finish_on_goal=None):
     return results
 
 
-def deconflict(planners, radii, order=None, start=0, max_wait=0):
+def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False):
     """
     Prioritised planning over the trees as they stand: in `order` (default: as listed) every planner picks, with Planner.avoid, the
     best plan of its tree that stays clear of the plans of the planners before it -- each of those a disc of its radius that moves
@@ -1498,7 +1517,21 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0):
 
     Returns one entry per planner, in the order of `planners`: avoid's dict, or None for the first of the order and for a planner
     without a tree on the device.  It costs one device call per planner after the first: a planner's tracks are the plans the
-    earlier ones ended up with, so the priority order makes the calls sequential by nature; nothing is batched across planners.
+    earlier ones ended up with, so the priority order makes the calls sequential by nature; by default nothing is batched across
+    planners.
+
+    `batched=True` gives the same results, plans and dicts through launches that span the trees (avoids' calls,
+    csrc/clear_multi.hpp), in rounds: every planner keeps a candidate plan -- on entry the one it holds --, a round asks all
+    "dirty" planners in ONE batched call, each against the current candidates of those before it, and a planner is dirty in the
+    next round iff a candidate before it changed; the first round asks everybody but the first of the order, the loop ends when
+    nothing changed, and the plans are adopted once, at the end.  The fixed point is the sequential answer: by induction,
+    position r of the order is final after round r -- the positions before it were final one round earlier, so in round r it is
+    asked against exactly the tracks the loop would show it, or it was asked against them before and nothing has changed since --
+    so there are at most n - 1 rounds.  What it costs: in the worst case (every round changes only the next position) each round
+    checks every tree behind the change again, n (n - 1) / 2 tree checks instead of the loop's n - 1, in exchange for rounds of
+    one launch sequence each instead of n - 1 dependent calls; when the first answers already stand -- traffic that rarely
+    conflicts -- it is two rounds, or one.  What avoid refuses with RuntimeError (the goal changed) is a ValueError then, raised
+    before any planner is touched, as in avoids.
 
     Refused with ValueError before any planner is touched: planners that do not share `dt`, a planner twice, an `order` that is no
     permutation, `radii` of the wrong shape or negative, a `max_wait` that is no integer in 0 .. 63, a planner without a plan (it
@@ -1529,6 +1562,8 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0):
     for k, p in enumerate(planners):
         if getattr(p, "x_seq", None) is None or len(p.x_seq) < 1:
             raise ValueError("deconflict: planner %d has no plan; it cannot be a track." % k)
+    if batched:
+        return _deconflict_batched(planners, r, order, int(start), max_wait)[0]
     results = [None] * n
     for at, k in enumerate(order):
         if at == 0:
@@ -1537,3 +1572,163 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0):
         tracks = [np.asarray(planners[j].x_seq, dtype=np.float64)[:, :2] for j in before]
         results[k] = planners[k].avoid(tracks, r[before], start, max_wait=max_wait)
     return results
+
+
+def _deconflict_rounds(order, entry, ask):
+    """
+    The schedule of deconflict(batched=True), with nothing of the device in it.  `order`: the priority order (planner indices);
+    `entry`: per planner (by index) the candidate it comes with -- any value that compares with ==; ask(ks, candidates): for the
+    planners `ks` (in the order's order) their answers as (candidate, answer) pairs, planner k asked against candidates[j] of the
+    planners j before it in the order -- one batched launch; `answer` is kept for the caller and not looked at here.
+
+    Round 1 asks everybody but the first of the order; a planner is asked again in the next round iff the candidate of a planner
+    before it changed in this one, i.e. the planners behind the earliest change are.  The loop ends when a round changed nothing.
+    Why the fixed point is the sequential answer, by induction on the position r in the order: position 0 is never asked, so it is
+    final from the start; if the positions before r are final after round r - 1, then in round r position r is either asked against
+    exactly the candidates the sequential loop would show it, or it is not dirty -- nothing before it has changed since it was
+    last asked -- and the answer it holds is already that one.  So position r is final after round r, a change in round r lies at a
+    position >= r, and after at most n - 1 rounds nothing is dirty.
+
+    Returns (candidates, answers, log): the final candidate and the last answer per planner (None where never asked) and, per
+    round, the list of planners asked.
+    """
+    order = list(order)
+    cand, answers, log = list(entry), [None] * len(entry), []
+    dirty = order[1:]
+    while dirty:
+        got = ask(list(dirty), list(cand))
+        log.append(list(dirty))
+        earliest = None
+        for k, (c, answer) in zip(dirty, got):
+            answers[k] = answer
+            if not c == cand[k]:
+                cand[k] = c
+                at = order.index(k)
+                earliest = at if earliest is None else min(earliest, at)
+        dirty = [] if earliest is None else order[earliest + 1:]
+    return cand, answers, log
+
+
+def _fleet_avoid_runs(name, planners):
+    """Every planner's _avoid_begin; what avoid refuses with RuntimeError is a ValueError here, raised before any planner is touched."""
+    try:
+        return [p._avoid_begin() for p in planners]
+    except RuntimeError as ex:
+        raise ValueError(str(ex).replace("avoid:", name + ":").replace("refine_plan:", name + ":"))
+
+
+def _avoids_query(planners, runs, tables, radii, starts, max_wait):
+    """The device calls of avoid for the planners that have a run, batched: per planner (counters, first, dwell) -- first / dwell the
+    plain query's per-node arrays at the current plan's departure, or None where the wait query shows that plan to be clear -- and
+    None for a planner without a run.  One native call per group of _fleet_groups, and with max_wait ONE more (the plain query for
+    the planners whose current plan is not clear).  Touches no planner.  Returns (results, native calls made)."""
+    res, calls = [None] * len(planners), 0
+    for members in _fleet_groups(planners, runs):
+        pick = lambda seq, ks: [seq[k] for k in ks]
+        engines = [planners[k]._engine for k in members]
+        if max_wait == 0:
+            got = Engine.tree_clear_multi(engines, pick(tables, members), pick(radii, members), pick(starts, members), per_node=True)
+            calls += 1
+            for k, g in zip(members, got):
+                res[k] = g
+            continue
+        got = Engine.tree_clear_wait_multi(engines, pick(tables, members), pick(radii, members), pick(starts, members), max_wait + 1,
+                                           per_node=True)
+        calls += 1
+        again = []
+        for k, (out, clear, dwell_ok) in zip(members, got):
+            res[k] = (out, None, None)
+            if not planners[k]._avoid_plan_holds(runs[k], clear, dwell_ok, max_wait):
+                again.append(k)
+        if again:                                                   # the time of their plans' first conflict: the plain query, once for all
+            got = Engine.tree_clear_multi([planners[k]._engine for k in again], pick(tables, again), pick(radii, again),
+                                          [starts[k] + planners[k].plan_wait for k in again], per_node=True)
+            calls += 1
+            for k, (_, first, dwell) in zip(again, got):
+                res[k] = (res[k][0], first, dwell)
+    return res, calls
+
+
+def avoids(planners, tracks, radii, start=0, adopt=True, max_wait=0):
+    """
+    avoid for a fleet: every planner gets exactly what its own avoid(tracks, radii, start, adopt, max_wait) returns and leaves --
+    the dict (plan_first included), the adopted plan, plan_wait, plan_reached_goal, the dropped finish_on_goal tail, None for a
+    planner without a tree of its own on the device -- but the device calls are shared: the planners of one (device, native system
+    type) form a group, and a group's trees are checked in ONE native call (Engine.tree_clear_multi / tree_clear_wait_multi,
+    csrc/clear_multi.hpp: every stage one launch that spans the trees), in slices of 128.  With `max_wait` the planners whose
+    current plan is not clear get the plain query at their plan's departure, for plan_first, in ONE further call per group.
+    `tracks`, `radii`: one set for everybody, as avoid takes it -- the shared-traffic case: the table is uploaded once per launch,
+    not once per tree -- or a list with one such entry per planner (tracks: a list of len(planners) entries, each an array
+    (L, D, 2) or a list of D arrays (L_d, 2); radii: the matching list).  The trees are never modified.
+
+    Refused before any planner is touched: everything avoid refuses (a changed goal, which avoid refuses with RuntimeError, is a
+    ValueError here, as in the other fleet calls), a planner that appears twice, an object that is no Planner, per-planner tracks
+    without per-planner radii.  Callback mode raises NotImplementedError, as in deconflict.
+    """
+    planners = list(planners)
+    n = len(planners)
+    if len(set(id(p) for p in planners)) != n:
+        raise ValueError("avoids: a planner appears twice.")
+    for k, p in enumerate(planners):
+        if not isinstance(p, Planner):
+            raise ValueError("avoids: expected Planner objects.")
+        if p.callback_mode:
+            raise NotImplementedError("avoids: planner %d is in callback mode; the device cannot call its Python feasibility test." % k)
+    per = n > 0 and isinstance(tracks, (list, tuple)) and len(tracks) == n and all(isinstance(t, (list, tuple)) or np.ndim(t) == 3 for t in tracks)
+    if per:
+        if not isinstance(radii, (list, tuple, np.ndarray)) or len(radii) != n:
+            raise ValueError("avoids: tracks per planner need radii per planner (a list of %d entries)." % n)
+        tabs = [Engine.track_table(tracks[k], radii[k], start) for k in range(n)]
+    else:
+        tabs = [Engine.track_table(tracks, radii, start)] * n
+    max_wait = Engine.wait_count(max_wait, "max_wait", 0, 63)
+    if not planners:
+        return []
+    start = tabs[0][2]
+    runs = _fleet_avoid_runs("avoids", planners)
+    got, _ = _avoids_query(planners, runs, [t[0] for t in tabs], [t[1] for t in tabs], [start] * n, max_wait)
+    return [None if run is None else p._avoid_end(run, g[0], g[1], g[2], start, adopt) for p, run, g in zip(planners, runs, got)]
+
+
+def _deconflict_batched(planners, r, order, start, max_wait):
+    """deconflict's loop as rounds of batched launches (_deconflict_rounds has the schedule and why it ends at the loop's answer).
+    A candidate is (end node, wait) with its rows [:, :2]; on entry it is the plan the planner holds, and a planner without a clear
+    hit keeps that one.  Adoption happens once, at the end, from the last answer of every planner -- which was given against the
+    final candidates of those before it, and about the plan it held on entry.  Returns (results, rounds, native calls)."""
+    n = len(planners)
+    runs = _fleet_avoid_runs("deconflict", planners)
+    held = [(int(p.node_seq[-1]) if getattr(p, "node_seq", None) else -1, int(getattr(p, "plan_wait", 0))) for p in planners]
+    rows = [{held[k]: np.ascontiguousarray(np.asarray(p.x_seq, dtype=np.float64)[:, :2])} for k, p in enumerate(planners)]
+    calls = [0]
+
+    def rows_of(k, c):
+        if c not in rows[k]:                                        # the tree path of the hit, `wait` rows of its first row in front
+            p = planners[k]
+            x = np.asarray(p.tree.trajectory(p.tree.climb(c[0]))[0], dtype=np.float64)[:, :2]
+            rows[k][c] = np.ascontiguousarray(np.concatenate((np.repeat(x[:1], c[1], axis=0), x)))
+        return rows[k][c]
+
+    def ask(ks, cand):
+        asked = [k for k in ks if runs[k] is not None]              # (a planner without a tree on the device keeps its plan)
+        tables, radii = [None] * n, [None] * n
+        for k in asked:
+            before = order[:order.index(k)]
+            tables[k], radii[k], _ = Engine.track_table([rows_of(j, cand[j]) for j in before], r[before], start)
+        sub = [runs[k] if k in asked else None for k in range(n)]
+        got, made = _avoids_query(planners, sub, tables, radii, [start] * n, max_wait)
+        calls[0] += made
+        out = []
+        for k in ks:
+            if got[k] is None:
+                out.append((cand[k], None))
+            else:
+                best = got[k][0]
+                out.append(((int(best["best_end"]), int(best.get("best_wait", 0))) if best["best_end"] >= 0 else held[k], got[k]))
+        return out
+
+    _, answers, log = _deconflict_rounds(order, held, ask)
+    results = [None] * n
+    for k in order[1:]:
+        if answers[k] is not None:
+            results[k] = planners[k]._avoid_end(runs[k], answers[k][0], answers[k][1], answers[k][2], start, True)
+    return results, len(log), calls[0]
