@@ -377,6 +377,45 @@ int lqrrt_tree_clear_wait_multi(lqrrt_engine** engines, int n, const double* con
                                 const int32_t* L, const int32_t* D, const int32_t* start, const int32_t* waits,
                                 lqrrt_clear_wait_stats* out /*[n]*/, uint64_t* const* clear_host, uint64_t* const* dwell_host, void* stream);
 
+/* lqrrt_tree_clear and lqrrt_connect_search in one call (Planner.avoid(connect); DESIGN.md section 19;
+ * tests/clear_connect_reference.py): when every goal hit of the tree is crossed by the discs, or only a long one is clear, which
+ * node whose root path is clear reaches the goal by a short chain of goal-directed steers that stays clear too?  Everything of
+ * lqrrt_tree_clear holds unchanged and is computed first -- cum, tau, the clamp min(tau, L - 1), the row test against the D discs
+ * of that instant alone, first, dwell, best and every counter of *out.  On top of that:
+ *   incumbent  = depth of the best clear hit in lqrrt_connect_search's cost units (depth[0] = 1, depth[v] = depth[pID[v]] + edge
+ *                length of v, so depth = cum - edge length of the root + 1); 2^31 - 1 without a clear hit.  None is passed in.
+ *   candidate  = a node v with first[v] == -1: every such node, or those among nodes_host[count] (NULL: every node).  The
+ *                propagated first counts: a node below a conflict is no candidate; the root is one when its row passes at start.
+ *   chain      = exactly lqrrt_connect_search's: up to goal_tries steers at the goal against the STATIC map with the fixed horizon
+ *                horizon_iters, an empty edge ends it, valid when an edge ends strictly inside the goal box.  The discs cut no
+ *                edge, they accept or reject the chain: lqrrt_connect_commit(v, goal_tries, horizon_iters), unchanged, replays
+ *                exactly the chain that was judged.
+ *   time       = row k of the chain's j-th non-empty edge has tau = start + cum[v] + (rows of the chain's earlier edges) + k,
+ *                which is the time lqrrt_tree_clear gives that row after a commit.  A chain is clear when every row of every edge
+ *                passes at its tau and its last row passes at every tau' in [start + cum[v] + chain rows, L - 1] (the wait at the
+ *                goal; an empty range passes).
+ *   winner     = the valid and clear candidate of smallest (cost, v) with cost = depth[v] + chain rows < incumbent -- strictly: a
+ *                chain that only ties with the best clear hit does not win.  The search stops a chain early as
+ *                lqrrt_connect_search does (key cost << 32 | v, seeded with incumbent << 32, lowered by valid and clear chains
+ *                only), so the winner depends neither on scheduling nor on the order of the id list.
+ * Reads only and synchronous, as lqrrt_tree_clear: all device memory of the call is one transient allocation, and everything is
+ * enqueued back to back on the stream with one wait.  Every argument is checked before anything is allocated or enqueued:
+ * first lqrrt_tree_clear's refusals in their order, then lqrrt_connect_search's (goal_tries < 1, horizon_iters outside the edge
+ * pools, an id outside the tree, depths beyond 32 bits), then LQRRT_E_ARG when the search's LDS -- the refinement's layout plus
+ * 16 V bytes of hull points for the disc test -- exceeds the device's limit.  A refused call writes nothing into any output. */
+typedef struct {
+    int32_t clear_candidates; /* candidates with first == -1 (entries of the id list, or nodes)       */
+    int32_t chain_from;       /* v, the winning candidate; -1 without a winner                        */
+    int32_t chain_rows;       /* rows of the winning chain; -1 without                                */
+    int32_t reserved;
+    int64_t chain_cost;       /* depth[v] + chain rows; -1 without                                    */
+    int64_t chain_arrival;    /* cum[v] + chain rows: best_steps after a commit; -1 without           */
+} lqrrt_clear_connect_stats;
+int lqrrt_tree_clear_connect(lqrrt_engine* e, const double* tracks_host, const double* radii_host, int L, int D, int start,
+                             int horizon_iters, int goal_tries, const int32_t* nodes_host, int count /* nodes_host NULL: every node */,
+                             lqrrt_clear_stats* out, lqrrt_clear_connect_stats* chain, int32_t* first_host, int32_t* dwell_host,
+                             void* stream);
+
 /* Overwrites the ignore bits of nodes [first, first+count) (planner.py:270 `ignores`). */
 int lqrrt_tree_set_ignored(lqrrt_engine* e, int first, int count, const uint8_t* flags_host);
 

@@ -80,6 +80,14 @@ class ClearWaitStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ClearConnectStats(C.Structure):
+    _fields_ = [("clear_candidates", C.c_int32), ("chain_from", C.c_int32), ("chain_rows", C.c_int32), ("reserved", C.c_int32),
+                ("chain_cost", C.c_int64), ("chain_arrival", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("clear_candidates", "chain_from", "chain_cost", "chain_rows", "chain_arrival")}
+
+
 # every symbol include/lqrrt_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I, _I64, _D = C.c_int, C.c_int64, C.c_double
@@ -112,6 +120,8 @@ SIGNATURES = {
     "lqrrt_tree_clear_wait": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(ClearWaitStats), _P, _P, _P]),
     "lqrrt_tree_clear_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_tree_clear_wait_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lqrrt_tree_clear_connect": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, C.POINTER(ClearStats), C.POINTER(ClearConnectStats), _P, _P,
+                                      _P]),
     "lqrrt_tree_get_edges": (_I, [_P, _I, _I, _P, _P]),
     "lqrrt_tree_mark": (_I, [_P]),
     "lqrrt_tree_rewind": (_I, [_P]),

@@ -283,6 +283,32 @@ class Engine(object):
         Reads only: tree, goal bookkeeping and footprint stay as they are."""
         return self._clear("lqrrt_tree_clear", nat.ClearStats, np.int32, tracks, radii, start, None, per_node)
 
+    def tree_clear_connect(self, tracks, radii, start, horizon_iters, tries=8, nodes=None, per_node=False):
+        """tree_clear and connect_search in one native call (lqrrt_tree_clear_connect; the rule: tests/clear_connect_reference.py):
+        besides tree_clear's answer, the node whose root path is clear of the discs and whose goal chain -- up to `tries` steers at
+        the goal with the fixed horizon `horizon_iters`, as connect_search makes them -- stays clear of them at its own times, waits
+        at the goal unharmed and gives a plan strictly shorter than the best clear hit.  `nodes`: None (every node) or an id list.
+        Returns (stats, chain) and with `per_node` also first [N] and dwell_first [N]: `stats` is tree_clear's dict, `chain` holds
+        clear_candidates (candidates whose root path is clear), chain_from (the winner, -1: none), chain_cost (steps from the root,
+        the root's included), chain_rows and chain_arrival (best_steps after connect_commit(chain_from, horizon_iters, tries)).
+        Reads only: tree, goal bookkeeping and footprint stay as they are."""
+        table, r, start = self.track_table(tracks, radii, start)
+        ids, ids_ptr, count = self._id_list(nodes)
+        if ids is not None and count == 0:
+            ids = np.zeros(1, dtype=np.int32)                     # (an empty list still has an address)
+            ids_ptr = nat.ptr(ids)
+        st, ch = nat.ClearStats(), nat.ClearConnectStats()
+        a = b = None
+        if per_node:
+            n = max(self.size, 1)
+            a, b = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_tree_clear_connect(self.h, nat.ptr(table), nat.ptr(r), table.shape[0], table.shape[1], start,
+                                                     int(horizon_iters), int(tries), ids_ptr, count, C.byref(st), C.byref(ch),
+                                                     None if a is None else nat.ptr(a), None if b is None else nat.ptr(b), self._stream()))
+        if per_node:
+            return st.as_dict(), ch.as_dict(), a[:st.size], b[:st.size]
+        return st.as_dict(), ch.as_dict()
+
     @staticmethod
     def wait_count(waits, what="waits", lo=1, hi=64):
         """`waits` as an integer in lo .. hi, or ValueError.  Host only."""

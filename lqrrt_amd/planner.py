@@ -801,7 +801,7 @@ class Planner:
         return True
 
     # ------------------------------------------------------------------------------------------ moving obstacles
-    def avoid(self, tracks, radii, start=0, adopt=True, max_wait=0):
+    def avoid(self, tracks, radii, start=0, adopt=True, max_wait=0, connect=0):
         """
         Which plan in the tree stays clear of obstacles that move?  Not in the reference, whose ROS node re-evaluates its one
         plan on the host.  `tracks` gives the centres (world x, y) of D discs at consecutive instants spaced by `dt`: an array
@@ -819,9 +819,9 @@ class Planner:
         there; a finish_on_goal tail is not part of the check), None when that plan is clear.  With `adopt` and a clear hit the
         plan becomes that hit's root path (node_seq, x_seq, u_seq, t_seq, T, the interpolators) and plan_reached_goal is set; a
         finish_on_goal tail is not applied to it, because it would not have been checked.  Otherwise the plan is untouched.
-        The tree is never modified.  Returns None when there is no tree of this planner on the device (refine_plan's condition).
-        Not covered: chains that connect_goal / connect_via / retarget appended are tested like any other edge, but nothing is
-        appended here; waiting anywhere but at the start; obstacles that are not discs.
+        The tree is never modified (but for `connect`, below).  Returns None when there is no tree of this planner on the device
+        (refine_plan's condition).  Not covered: chains that connect_goal / connect_via / retarget appended are tested like any
+        other edge, but without `connect` nothing is appended here; waiting anywhere but at the start; obstacles that are not discs.
 
         `max_wait` in 1 .. 63 also asks "and if I left later?": the vehicle may stand on the plan's first row (the root's) for
         w = 0 .. max_wait rows of dt and follow the tree w rows later; while it stands there the root's row is tested at every
@@ -835,15 +835,36 @@ class Planner:
         first x_seq and u_seq rows stand in front of it: node_seq is the tree path as ever, T, t_seq and the interpolators go
         over the longer sequence, and `plan_wait` = best_wait says how many rows are the wait (0 after every other call that sets
         a plan).  With max_wait = 0 the call, its cost and its dict are what they were.
+
+        `connect` = goal_tries >= 1 (with max_wait = 0) also asks the nodes that are NOT goal hits: every node whose root path is
+        clear is a candidate of connect_goal's search -- up to `connect` steers at the goal with the fixed horizon `horizon_iters`,
+        against the static map -- and its chain is accepted only when every row of it is clear of the discs at the time the
+        vehicle would be on it, the wait at the goal included, and the plan it gives is strictly shorter than the best clear hit
+        (any such chain wins when no hit is clear).  The discs cut no edge: they accept or reject a chain.  Still ONE call on the
+        device (csrc/clear_connect.hpp; tests/clear_connect_reference.py restates the rule).  The dict gains clear_candidates,
+        chain_from (the node the winning chain leaves from, -1: none), chain_cost (steps from the root, the root's row included),
+        chain_rows, chain_arrival (best_steps of the plan the chain gives) and chain_committed.  With `adopt` and a winning chain
+        its edges are appended to the tree below chain_from, as connect_goal appends them, and the plan becomes climb(chain_from) +
+        the new nodes, without a finish_on_goal tail (it would not have been checked); plan_reached_goal is set and plan_wait is 0.
+        THIS IS THE ONE CASE IN WHICH avoid MODIFIES THE TREE.  When the tree cannot hold the chain it stays as it is,
+        chain_committed is False and the best clear hit, if any, is adopted as without `connect`; so it is without a winning chain.
+        With adopt=False nothing is committed.  plan_first keeps its meaning: it refers to the plan held on entry.  Not covered:
+        `connect` together with `max_wait` (ValueError); chains through waypoints; a fleet (avoids).  connect = 0 keeps the call,
+        its cost and its dict what they were.
         """
         if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
             raise NotImplementedError("avoid: in callback mode the feasibility test is the user's Python function; the device "
                                       "cannot call it on the rows of the tree.")
         table, radii, start = Engine.track_table(tracks, radii, start)
         max_wait = Engine.wait_count(max_wait, "max_wait", 0, 63)
+        connect = Engine.wait_count(connect, "connect (goal tries)", 0, 2 ** 31 - 1)
+        if connect and max_wait:
+            raise ValueError("avoid: connect together with max_wait is not covered; ask one or the other.")
         run = self._avoid_begin()
         if run is None:
             return None
+        if connect:
+            return self._avoid_connect(run, table, radii, start, adopt, connect)
         if max_wait == 0:
             out, first, dwell = self._engine.tree_clear(table, radii, start, per_node=True)
         else:
@@ -865,6 +886,22 @@ class Planner:
         if self.goal is None or not np.array_equal(self.goal, self._grown_goal):
             raise RuntimeError("avoid: the goal changed since the tree was grown; use update_plan, replan or retarget.")
         return run
+
+    def _avoid_connect(self, run, table, radii, start, adopt, goal_tries):
+        """avoid(connect=goal_tries): one native call; a winning chain is committed and adopted as connect_goal's winner is, else
+        everything is avoid's own."""
+        eng = self._engine
+        out, chain, first, dwell = eng.tree_clear_connect(table, radii, start, run.H, goal_tries, per_node=True)
+        ids = None
+        if adopt and chain["chain_from"] >= 0:
+            ids = self._commit_winner(lambda: eng.connect_commit(chain["chain_from"], run.H, goal_tries))
+        out = self._avoid_end(run, out, first, dwell, start, adopt and ids is None)     # (plan_first: of the plan held on entry)
+        out.update(chain)
+        out["chain_committed"] = ids is not None
+        if ids is not None:
+            self._connect_accept(run, chain["chain_cost"], chain["chain_from"], ids, False)     # (no tail: it would not have been checked)
+            self.plan_wait = 0
+        return out
 
     def _avoid_plan_holds(self, run, clear, dwell_ok, max_wait):
         """From the wait query's masks: the current plan is clear as it stands, with the wait it was adopted with."""
