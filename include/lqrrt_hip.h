@@ -416,6 +416,27 @@ int lqrrt_tree_clear_connect(lqrrt_engine* e, const double* tracks_host, const d
                              lqrrt_clear_stats* out, lqrrt_clear_connect_stats* chain, int32_t* first_host, int32_t* dwell_host,
                              void* stream);
 
+/* lqrrt_tree_clear_connect for n trees in one call (lqrrt_amd.avoids(connect)).  Member k answers EXACTLY as
+ * lqrrt_tree_clear_connect(engines[k], tracks_host[k], radii_host[k], L[k], D[k], start[k], horizon_iters[k], goal_tries[k],
+ * nodes_host ? nodes_host[k] : NULL, counts[k], out + k, chain + k, first_host ? first_host[k] : NULL, dwell_host ? dwell_host[k] : NULL)
+ * does: the seven counters, first, dwell_first, the five chain fields, clear_candidates with its "entries of an id list are counted,
+ * not nodes" rule.  nodes_host: NULL, or per engine NULL (every node) or an id list of counts[k] entries (it may repeat ids, and it
+ * may be empty: the member then gets its clearance answer and no chain); counts is read only where a list is given.  Nothing of any
+ * tree is written; a winner is replayed by lqrrt_connect_commit(_multi).
+ * Execution: per chunk of up to 32 members one transient allocation and one uploaded image; the stages of lqrrt_tree_clear_multi,
+ * one launch each over the chunk; one launch that seeds every member's key; one search launch over the members' candidates back to
+ * back, every member with a key of its own (the early stop prunes within one tree only); the copies back.  The chunks are enqueued
+ * back to back and waited for once.  Members that pass the same tracks and radii arrays with equal L and D share one table.
+ * Refusals, all before anything is allocated or enqueued, the message naming the engine, and a refused call writes nothing into any
+ * output: no engines, a null argument (chain included), more than 128 engines, a null or generic engine, an engine twice, mixed
+ * device or model; then per member, in lqrrt_tree_clear_connect's order: lqrrt_tree_clear's refusals, lqrrt_connect_search's, an
+ * id list without its count, an id outside the tree, depths beyond 32 bits, the LDS of the search. */
+int lqrrt_tree_clear_connect_multi(lqrrt_engine** engines, int n, const double* const* tracks_host, const double* const* radii_host,
+                                   const int32_t* L, const int32_t* D, const int32_t* start, const int32_t* horizon_iters,
+                                   const int32_t* goal_tries, const int32_t* const* nodes_host /* NULL, or per engine NULL = every node */,
+                                   const int32_t* counts, lqrrt_clear_stats* out, lqrrt_clear_connect_stats* chain,
+                                   int32_t* const* first_host, int32_t* const* dwell_host, void* stream);
+
 /* Overwrites the ignore bits of nodes [first, first+count) (planner.py:270 `ignores`). */
 int lqrrt_tree_set_ignored(lqrrt_engine* e, int first, int count, const uint8_t* flags_host);
 

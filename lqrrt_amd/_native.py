@@ -122,6 +122,7 @@ SIGNATURES = {
     "lqrrt_tree_clear_wait_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_tree_clear_connect": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, C.POINTER(ClearStats), C.POINTER(ClearConnectStats), _P, _P,
                                       _P]),
+    "lqrrt_tree_clear_connect_multi": (_I, [_P, _I] + [_P] * 14),
     "lqrrt_tree_get_edges": (_I, [_P, _I, _I, _P, _P]),
     "lqrrt_tree_mark": (_I, [_P]),
     "lqrrt_tree_rewind": (_I, [_P]),

@@ -90,6 +90,7 @@ static int fail(int code, const char* fmt, ...) {
 #include "engine_clear_multi.hpp" // ABI: tree_clear_multi / tree_clear_wait_multi (avoids, deconflict(batched): the same for several trees per launch)
 #include "engine_connect.hpp"     // ABI: connect_search / connect_commit (Planner.connect_goal: goal chains from every tree node; + _multi)
 #include "engine_clear_connect.hpp" // ABI: tree_clear_connect (Planner.avoid(connect): goal chains from clear nodes that stay clear of the moving discs)
+#include "engine_clear_connect_multi.hpp" // ABI: tree_clear_connect_multi (avoids(connect): the same for several trees, on engine_clear_multi.hpp's host path)
 #include "engine_reach.hpp"       // ABI: reach_search / reach_commit (Planner.goal_costs / retarget: one tree asked about many goals)
 #include "engine_reach_multi.hpp" // ABI: reach_search_multi / reach_commit_multi (fleet_goal_costs / retargets: the same for several trees)
 #include "engine_connect_via.hpp" // ABI: connect_via_search / connect_via_commit (Planner.connect_via: goal chains through waypoints)

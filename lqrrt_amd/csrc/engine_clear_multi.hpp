@@ -63,17 +63,31 @@ struct ClearMember {
     int shares = -1;
 };
 
-// Every argument of every member, before anything is allocated or enqueued.  waits == nullptr: lqrrt_tree_clear_multi.
-template <class M>
+// What a caller adds to the two calls of this file (lqrrt_tree_clear_connect_multi adds its search: engine_clear_connect_multi.hpp).
+// To the check: more(k), what else it asks of member k, behind the solo call's refusals.  To the run, per chunk: workgroups of its
+// own per member (the chunks then hold fewer than 2^32 threads for its launch too), parts of its own in the uploaded image, what it
+// enqueues behind the select, copies back included; the run's one synchronise covers them.  ClearNoExtra: nothing of all that.
+struct ClearNoExtra {
+    long long groups(int) const { return 0; }
+    void carve(size_t, const MultiChunk&, Carve&) {}
+    template <class Desc>
+    void fill(size_t, const MultiChunk&, char*, char*, const Desc*) {}
+    int enqueue(size_t, const MultiChunk&, const ProtoTable&, char*, hipStream_t) { return 0; }
+};
+
+// Every argument of every member, before anything is allocated or enqueued.  waits == nullptr: lqrrt_tree_clear_multi.  `args`:
+// the caller's further arrays are all there.
+template <class M, class More>
 static int clear_multi_check(lqrrt_engine** engines, int n, const double* const* tracks, const double* const* radii, const int32_t* L,
                              const int32_t* D, const int32_t* start, const int32_t* waits, const typename M::Stats* out,
-                             std::vector<ClearMember>& mem) {
+                             std::vector<ClearMember>& mem, bool args, More more) {
     mem.resize(n > 0 ? (size_t)n : 0);
-    return multi_engines_check(engines, n, tracks && radii && L && D && start && out && (waits || !M::HIT_BYTES), [&](int k) {
+    return multi_engines_check(engines, n, tracks && radii && L && D && start && out && (waits || !M::HIT_BYTES) && args, [&](int k) {
         ClearMember& me = mem[(size_t)k];
         const int rc = clear_check<typename M::Solo>(engines[k], out + k, tracks[k], radii[k], L[k], D[k], start[k], waits ? waits[k] : 1,
                                                      me.cum, me.table);
         if (rc) { g_err += engine_suffix(k); return rc; }
+        TRY(more(k));
         // the shared-traffic case: the same arrays, read the same way, make the same table -- keep one
         const bool novice = model_novice(engines[k]->model);
         for (int q = 0; q < k && me.shares < 0; ++q)
@@ -88,11 +102,11 @@ static int clear_multi_check(lqrrt_engine** engines, int n, const double* const*
 // a tree's per-node arrays come back in copies of their own from this size on
 static bool clear_multi_direct(size_t N) { return N >= 65536; }
 
-// The launches of a checked call, chunk by chunk, and the call's one synchronise.
-template <class M>
+// The launches of a checked call, chunk by chunk, and the call's one synchronise.  `extra`: see ClearNoExtra.
+template <class M, class X = ClearNoExtra>
 static int clear_multi_run(lqrrt_engine** engines, int n, const std::vector<ClearMember>& mem, const int32_t* L, const int32_t* D,
                            const int32_t* start, const int32_t* waits, typename M::Stats* out, typename M::Node* const* ans_host,
-                           typename M::Node* const* dwell_host, hipStream_t st) {
+                           typename M::Node* const* dwell_host, hipStream_t st, X&& extra = X()) {
     typedef typename M::Link Link;
     typedef typename M::Node Node;
     typedef typename M::Out Out;
@@ -101,7 +115,7 @@ static int clear_multi_run(lqrrt_engine** engines, int n, const std::vector<Clea
     for (int k = 0; k < n; ++k) {
         c_check[k] = engines[k]->N;
         c_node[k] = (engines[k]->N + RETAIN_BLOCK - 1) / RETAIN_BLOCK;
-        groups[k] = (long long)engines[k]->N * M::CHECK_GROUPS;
+        groups[k] = std::max((long long)engines[k]->N * M::CHECK_GROUPS, extra.groups(k));
     }
     std::vector<MultiChunk> chunks = multi_chunks(groups);
     // per chunk: where its parts lie, and the host side of what comes back per node
@@ -144,6 +158,7 @@ static int clear_multi_run(lqrrt_engine** engines, int n, const std::vector<Clea
             }
             o_table[q] = at >= 0 ? o_table[at] : carve(sizeof(double) * mem[owner].table.size());
         }
+        extra.carve(ci, c, carve);
         const size_t image = carve.off;
         const size_t o_a = carve(sizeof(RetainLink) * sumN), o_b = carve(sizeof(RetainLink) * sumN);
         const size_t o_ca = carve(sizeof(Link) * sumN), o_cb = carve(sizeof(Link) * sumN);
@@ -180,6 +195,7 @@ static int clear_multi_run(lqrrt_engine** engines, int n, const std::vector<Clea
             const std::vector<double>& table = mem[owner].table;
             memcpy(c.img.data() + o_table[q], table.data(), sizeof(double) * table.size());
         }
+        extra.fill(ci, c, c.img.data(), dm, (const Desc*)hd);
         HIPCHK(hipMemcpyAsync(dm, c.img.data(), image, hipMemcpyHostToDevice, st));
         const RetainDesc* d_rdesc = (const RetainDesc*)(dm + o_rdesc);
         const Desc* d_desc = (const Desc*)(dm + o_desc);
@@ -199,6 +215,7 @@ static int clear_multi_run(lqrrt_engine** engines, int n, const std::vector<Clea
         // ---- select
         M::select_multi(n_node, st, pt, d_desc, g_node);
         HIPCHK(hipGetLastError());
+        TRY(extra.enqueue(ci, c, pt, dm, st));
         // ---- back: the counters in one copy; the per-node arrays somebody asked for straight into the caller's memory where a
         // tree is large, and through ONE staged copy per kind for the small trees of the chunk (a copy per tree would cost them more
         // than it moves)
@@ -249,7 +266,7 @@ static int clear_multi_call(lqrrt_engine** engines, int n, const double* const* 
                             const int32_t* D, const int32_t* start, const int32_t* waits, typename M::Stats* out,
                             typename M::Node* const* ans_host, typename M::Node* const* dwell_host, void* stream) {
     std::vector<ClearMember> mem;
-    TRY(clear_multi_check<M>(engines, n, tracks, radii, L, D, start, waits, out, mem));
+    TRY(clear_multi_check<M>(engines, n, tracks, radii, L, D, start, waits, out, mem, true, [](int) { return 0; }));
     TRY(use_device(engines[0]));
     return clear_multi_run<M>(engines, n, mem, L, D, start, waits, out, ans_host, dwell_host, (hipStream_t)stream);
 }

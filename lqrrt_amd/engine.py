@@ -361,9 +361,24 @@ class Engine(object):
                                    per_node)
 
     @staticmethod
-    def _clear_multi(call, stats, dtype, engines, tables, radii, starts, waits, per_node):
-        """tree_clear_multi (`waits` None) and tree_clear_wait_multi: every engine's arguments checked in the solo calls' order, one
-        native call, and per engine what _clear returns."""
+    def tree_clear_connect_multi(engines, tables, radii, starts, horizons, tries=8, nodes=None, per_node=False):
+        """tree_clear_connect for n engines in one native call (lqrrt_tree_clear_connect_multi; csrc/clear_connect_multi.hpp):
+        tree_clear_multi's stages, then ONE launch that seeds every tree's key and ONE search launch over the candidates of all
+        trees, every tree with a key of its own; one allocation per chunk of 32 and one wait per call.  `tables`, `radii`, `starts`:
+        as tree_clear_multi takes them (the same table and radii objects share one upload); `horizons`: one per engine; `tries`:
+        one for all or one per engine; `nodes`: None, or one entry per engine, each None (every node) or an id list (it may repeat
+        ids; an empty one: the clearance answer and no chain).  Returns, per engine, exactly what its own tree_clear_connect(
+        tables[k], radii[k], starts[k], horizons[k], tries[k], nodes[k], per_node) returns.  The engines share device and model.
+        Every argument of every engine is checked before anything is launched (ValueError / NativeError as tree_clear_connect, the
+        message naming the engine); nothing of any tree is written."""
+        return Engine._clear_multi("lqrrt_tree_clear_connect_multi", nat.ClearStats, np.int32, engines, tables, radii, starts, None,
+                                   per_node, connect=(horizons, tries, nodes))
+
+    @staticmethod
+    def _clear_multi(call, stats, dtype, engines, tables, radii, starts, waits, per_node, connect=None):
+        """tree_clear_multi (`waits` None), tree_clear_wait_multi and tree_clear_connect_multi (`connect`: horizons, tries, nodes):
+        every engine's arguments checked in the solo calls' order, one native call, and per engine what _clear / tree_clear_connect
+        returns."""
         engines = list(engines)
         n = len(engines)
         if n < 1:
@@ -391,6 +406,18 @@ class Engine(object):
         if np.any(st0 > 2 ** 31 - 1):
             raise ValueError("start leaves 31 bits.")
         st0 = st0.astype(np.int32)
+        chain, keep = None, None
+        if connect is not None:
+            horizons, tries, nodes = connect
+            horizons = np.ascontiguousarray([int(h) for h in horizons], dtype=np.int32)
+            if horizons.shape != (n,):
+                raise ValueError("expected one horizon per engine")
+            tries = [tries] * n if isinstance(tries, (int, np.integer)) else list(tries)
+            if len(tries) != n:
+                raise ValueError("expected one goal_tries, or one per engine")
+            tries = np.ascontiguousarray([int(t) for t in tries], dtype=np.int32)
+            keep, node_ptrs, counts_ptr = Engine._id_lists(nodes, n)
+            chain = (nat.ClearConnectStats * n)()
         handles = (C.c_void_p * n)(*[e.h for e in engines])
         t_ptrs = (C.c_void_p * n)(*[t.ctypes.data for t, _ in tabs])
         r_ptrs = (C.c_void_p * n)(*[r.ctypes.data for _, r in tabs])
@@ -402,6 +429,13 @@ class Engine(object):
             a_ptrs = (C.c_void_p * n)(*[x.ctypes.data for x in a])
             b_ptrs = (C.c_void_p * n)(*[x.ctypes.data for x in b])
         extra = () if waits is None else (nat.ptr(waits),)
+        if connect is not None:
+            nat.check(getattr(nat.lib(), call)(handles, n, t_ptrs, r_ptrs, nat.ptr(Ls), nat.ptr(Ds), nat.ptr(st0), nat.ptr(horizons),
+                                               nat.ptr(tries), node_ptrs, counts_ptr, out, chain, a_ptrs, b_ptrs, engines[0]._stream()))
+            del keep                                              # (the id lists lived until here)
+            if per_node:
+                return [(out[k].as_dict(), chain[k].as_dict(), a[k][:out[k].size], b[k][:out[k].size]) for k in range(n)]
+            return [(out[k].as_dict(), chain[k].as_dict()) for k in range(n)]
         nat.check(getattr(nat.lib(), call)(handles, n, t_ptrs, r_ptrs, nat.ptr(Ls), nat.ptr(Ds), nat.ptr(st0), *extra, out, a_ptrs, b_ptrs,
                                            engines[0]._stream()))
         if per_node:

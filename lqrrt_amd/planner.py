@@ -849,8 +849,8 @@ class Planner:
         THIS IS THE ONE CASE IN WHICH avoid MODIFIES THE TREE.  When the tree cannot hold the chain it stays as it is,
         chain_committed is False and the best clear hit, if any, is adopted as without `connect`; so it is without a winning chain.
         With adopt=False nothing is committed.  plan_first keeps its meaning: it refers to the plan held on entry.  Not covered:
-        `connect` together with `max_wait` (ValueError); chains through waypoints; a fleet (avoids).  connect = 0 keeps the call,
-        its cost and its dict what they were.
+        `connect` together with `max_wait` (ValueError); chains through waypoints.  A fleet asks avoids(connect=...), which shares
+        the native calls.  connect = 0 keeps the call, its cost and its dict what they were.
         """
         if self.callback_mode:                                      # (as the last set_system left it; _resolve_mode would drop the plan)
             raise NotImplementedError("avoid: in callback mode the feasibility test is the user's Python function; the device "
@@ -895,6 +895,11 @@ class Planner:
         ids = None
         if adopt and chain["chain_from"] >= 0:
             ids = self._commit_winner(lambda: eng.connect_commit(chain["chain_from"], run.H, goal_tries))
+        return self._avoid_connect_end(run, out, chain, first, dwell, start, adopt, ids)
+
+    def _avoid_connect_end(self, run, out, chain, first, dwell, start, adopt, ids):
+        """What avoid(connect) and avoids(connect) share behind their native calls: the dict of one query's answer and, with the
+        new node ids `ids` of a committed chain (None: none was committed), its adoption."""
         out = self._avoid_end(run, out, first, dwell, start, adopt and ids is None)     # (plan_first: of the plan held on entry)
         out.update(chain)
         out["chain_committed"] = ids is not None
@@ -1541,7 +1546,7 @@ def retargets(planners, goals, goal_tries=8, nodes=None, finish_on_goal=None):
     return results
 
 
-def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False):
+def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False, connect=0):
     """
     Prioritised planning over the trees as they stand: in `order` (default: as listed) every planner picks, with Planner.avoid, the
     best plan of its tree that stays clear of the plans of the planners before it -- each of those a disc of its radius that moves
@@ -1570,6 +1575,11 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False):
     conflicts -- it is two rounds, or one.  What avoid refuses with RuntimeError (the goal changed) is a ValueError then, raised
     before any planner is touched, as in avoids.
 
+    `connect` = goal_tries >= 1 is avoid's as well: the sequential form hands it to every Planner.avoid, and a planner that adopts
+    a goal chain is then a track with that chain's rows for the planners after it.  Not covered, and refused with ValueError:
+    `connect` with batched=True -- a chain candidate has no rows in any tree until it is committed, and the rounds adopt only at
+    the end -- and `connect` together with `max_wait`, as in avoid.
+
     Refused with ValueError before any planner is touched: planners that do not share `dt`, a planner twice, an `order` that is no
     permutation, `radii` of the wrong shape or negative, a `max_wait` that is no integer in 0 .. 63, a planner without a plan (it
     cannot be a track).  Callback mode raises
@@ -1591,6 +1601,12 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False):
     if int(start) != start or int(start) < 0:
         raise ValueError("deconflict: start must be an integer >= 0.")
     max_wait = Engine.wait_count(max_wait, "deconflict: max_wait", 0, 63)
+    connect = Engine.wait_count(connect, "deconflict: connect (goal tries)", 0, 2 ** 31 - 1)
+    if connect and max_wait:
+        raise ValueError("deconflict: connect together with max_wait is not covered; ask one or the other.")
+    if connect and batched:
+        raise ValueError("deconflict: connect with batched=True is not covered: a chain has no rows in any tree until it is "
+                         "committed, and the rounds adopt only at the end.")
     for k, p in enumerate(planners):
         if p.callback_mode:
             raise NotImplementedError("deconflict: planner %d is in callback mode; the device cannot call its Python feasibility test." % k)
@@ -1607,7 +1623,7 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False):
             continue
         before = order[:at]
         tracks = [np.asarray(planners[j].x_seq, dtype=np.float64)[:, :2] for j in before]
-        results[k] = planners[k].avoid(tracks, r[before], start, max_wait=max_wait)
+        results[k] = planners[k].avoid(tracks, r[before], start, max_wait=max_wait, connect=connect)
     return results
 
 
@@ -1686,7 +1702,7 @@ def _avoids_query(planners, runs, tables, radii, starts, max_wait):
     return res, calls
 
 
-def avoids(planners, tracks, radii, start=0, adopt=True, max_wait=0):
+def avoids(planners, tracks, radii, start=0, adopt=True, max_wait=0, connect=0):
     """
     avoid for a fleet: every planner gets exactly what its own avoid(tracks, radii, start, adopt, max_wait) returns and leaves --
     the dict (plan_first included), the adopted plan, plan_wait, plan_reached_goal, the dropped finish_on_goal tail, None for a
@@ -1696,9 +1712,18 @@ def avoids(planners, tracks, radii, start=0, adopt=True, max_wait=0):
     current plan is not clear get the plain query at their plan's departure, for plan_first, in ONE further call per group.
     `tracks`, `radii`: one set for everybody, as avoid takes it -- the shared-traffic case: the table is uploaded once per launch,
     not once per tree -- or a list with one such entry per planner (tracks: a list of len(planners) entries, each an array
-    (L, D, 2) or a list of D arrays (L_d, 2); radii: the matching list).  The trees are never modified.
+    (L, D, 2) or a list of D arrays (L_d, 2); radii: the matching list).  The trees are never modified (but for `connect`).
 
-    Refused before any planner is touched: everything avoid refuses (a changed goal, which avoid refuses with RuntimeError, is a
+    `connect` = goal_tries >= 1 (with max_wait = 0) is avoid's: every planner gets exactly what its own avoid(..., connect=connect)
+    returns and leaves -- the dict with the five chain fields and chain_committed, plan_first of the plan held on entry, the committed
+    chain and the adopted plan, plan_wait = 0, plan_reached_goal.  A group makes ONE query (Engine.tree_clear_connect_multi,
+    csrc/clear_connect_multi.hpp: the clearance stages, one seed and one search launch over all its trees, every tree with a key of
+    its own) and then, over the members that have `adopt` and a winning chain, ONE commit (Engine.connect_commit_multi), as
+    connect_goals does it.  A member whose tree cannot hold its chain gets chain_committed = False and adopts its best clear hit as
+    without `connect`.  If a native commit call fails, the planners that did commit adopt their plans, then the error is raised.
+    connect = 0 keeps the calls and the dicts what they were.
+
+    Refused before any planner is touched: `connect` together with `max_wait`; everything avoid refuses (a changed goal, which avoid refuses with RuntimeError, is a
     ValueError here, as in the other fleet calls), a planner that appears twice, an object that is no Planner, per-planner tracks
     without per-planner radii.  Callback mode raises NotImplementedError, as in deconflict.
     """
@@ -1719,12 +1744,38 @@ def avoids(planners, tracks, radii, start=0, adopt=True, max_wait=0):
     else:
         tabs = [Engine.track_table(tracks, radii, start)] * n
     max_wait = Engine.wait_count(max_wait, "max_wait", 0, 63)
+    connect = Engine.wait_count(connect, "connect (goal tries)", 0, 2 ** 31 - 1)
+    if connect and max_wait:
+        raise ValueError("avoids: connect together with max_wait is not covered; ask one or the other.")
     if not planners:
         return []
     start = tabs[0][2]
     runs = _fleet_avoid_runs("avoids", planners)
+    if connect:
+        return _avoids_connect(planners, runs, [t[0] for t in tabs], [t[1] for t in tabs], start, adopt, connect)
     got, _ = _avoids_query(planners, runs, [t[0] for t in tabs], [t[1] for t in tabs], [start] * n, max_wait)
     return [None if run is None else p._avoid_end(run, g[0], g[1], g[2], start, adopt) for p, run, g in zip(planners, runs, got)]
+
+
+def _avoids_connect(planners, runs, tables, radii, start, adopt, goal_tries):
+    """avoids(connect=goal_tries) behind its checks: per group of _fleet_groups ONE query and, over the members with `adopt` and a
+    winning chain, ONE commit; then every planner's own _avoid_connect_end."""
+    results = [None] * len(planners)
+    pick = lambda seq, ks: [seq[k] for k in ks]
+    for mine in _fleet_groups(planners, runs):
+        got = Engine.tree_clear_connect_multi([planners[k]._engine for k in mine], pick(tables, mine), pick(radii, mine),
+                                              [start] * len(mine), [runs[k].H for k in mine], goal_tries, per_node=True)
+        winners = [(k, g[1]["chain_from"]) for k, g in zip(mine, got) if adopt and g[1]["chain_from"] >= 0]
+        new, failed = {}, None
+        if winners:
+            ids, failed = _fleet_commit(lambda: Engine.connect_commit_multi(
+                [planners[k]._engine for k, _ in winners], [v for _, v in winners], [runs[k].H for k, _ in winners], goal_tries))
+            new = {k: i for (k, _), i in zip(winners, ids)}         # (None: capacity, or a failed chain -- that tree is unchanged)
+        for k, (out, chain, first, dwell) in zip(mine, got):
+            results[k] = planners[k]._avoid_connect_end(runs[k], out, chain, first, dwell, start, adopt, new.get(k))
+        if failed is not None:
+            raise failed
+    return results
 
 
 def _deconflict_batched(planners, r, order, start, max_wait):
