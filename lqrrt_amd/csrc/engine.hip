@@ -13,7 +13,8 @@
 //  LQRRT_BENCH_EVENTS_EVERY -- bench.py; LQRRT_TORQUE_VMIN -- default of the boats' torque_vmin, lqrrt_amd/systems.py, the one
 //  lever that is a PARAMETER of the problem: it changes the arithmetic of the heading torque below that speed)
 // Compile-time (measurement builds only): -DSTEER_TIMING (device timestamps and placement counters in k_steer,
-// tools/steer_phases_bench.py), -DLQRRT_NO_KERNARG_TOUCH (k_steer without the touch of its argument block), -DABL_* (ablations,
+// tools/steer_phases_bench.py), -DLQRRT_NO_KERNARG_TOUCH (k_steer without the touch of its argument block), -DLQRRT_NO_KERNARG_PRELOAD (k_steer's hot
+// header behind the by-value structs, where the dispatcher preloads none of it: steer.hpp), -DABL_* (ablations,
 // tools/ablate_steer.py), -DLQRRT_USER_SYSTEM='"header"' (an out-of-tree problem as LQRRT_MODEL_USER, tools/build_user_system.py).
 #include "../../include/lqrrt_hip.h"
 #include "kernels.hpp"
@@ -152,4 +153,16 @@ extern "C" int lqrrt_clock_probe(int device, double* shader_mhz, double* ns_depe
     return 0;
 }
 
-#include "measure_abi.hpp"       // -DSTEER_TIMING builds only: read-back of the device timestamps (tools/steer_phases_bench.py)
+// The round block's layout as the host lays it out (rounds.hpp round_layout; lqrrt_engine_create): byte offsets {ctl, M[2], lf[2],
+// par[2], stale[2], changed[2], bytes}.  A test hook, not part of include/lqrrt_hip.h: tests/test_steer_entry_cpu.py sets it against
+// the table the device pass of the compiler makes of the same function.
+extern "C" int lqrrt_debug_round_layout(int max_wave, long long* out12) {
+    if (max_wave < 1 || max_wave > 4096 || !out12) return fail(LQRRT_E_ARG, "1 <= max_wave <= 4096");
+    const RoundLayout rl = round_layout(max_wave);
+    const long long v[12] = {rl.ctl, rl.M[0], rl.M[1], rl.lf[0], rl.lf[1], rl.par[0], rl.par[1], rl.stale[0], rl.stale[1],
+                             rl.changed[0], rl.changed[1], rl.bytes};
+    memcpy(out12, v, sizeof v);
+    return 0;
+}
+
+#include "measure_abi.hpp"      // -DSTEER_TIMING builds only: read-back of the device timestamps (tools/steer_phases_bench.py)

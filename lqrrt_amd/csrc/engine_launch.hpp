@@ -328,8 +328,17 @@ template <class S> static int steer_wavefronts(int count) {
 template <class S, bool DENSE, int NWF>
 static void launch_steer_nwf(lqrrt_engine* e, int count, size_t lds, hipStream_t st, const EvPair& ev, const double* xs, const int* list,
                              int lo, const int* par, const int* list_count, const SteerFuse& f, const RoundArgs& ra) {
-    hipExtLaunchKernelGGL((k_steer<S, DENSE, NWF>), dim3(count), dim3(64 * NWF), lds, st, ev.a, ev.b, 0, e->P, e->geo, e->res, e->tv,
-                          e->d_rec, e->L, xs, list, lo, par, list_count, f, ra);
+    // the hot header (steer.hpp, at k_steer): what a launch's first loads need, ahead of the structs
+    const int hot = (list ? STEER_HOT_LIST : 0) | (list_count ? STEER_HOT_COUNT : 0) | (ra.gblk ? STEER_HOT_GATHERED : 0);
+    const int wm = ra.W | (e->maxW << 16), rnd = ra.on ? ra.round : -1;
+#ifndef LQRRT_NO_KERNARG_PRELOAD
+    const SteerCold cold{e->P, e->geo, e->res, e->tv, e->L, list, par, list_count, f, ra};
+    hipExtLaunchKernelGGL((k_steer<S, DENSE, NWF>), dim3(count), dim3(64 * NWF), lds, st, ev.a, ev.b, 0, e->d_rec, xs, f.part, e->d_round,
+                          lo, f.n_chunks, wm, rnd, e->L.R, hot, cold);
+#else
+    hipExtLaunchKernelGGL((k_steer<S, DENSE, NWF>), dim3(count), dim3(64 * NWF), lds, st, ev.a, ev.b, 0, e->P, e->geo, e->res, e->tv, e->L,
+                          list, par, list_count, f, ra, e->d_rec, xs, f.part, e->d_round, lo, f.n_chunks, wm, rnd, e->L.R, hot);
+#endif
 }
 template <class S>
 static void launch_steer_kernel(lqrrt_engine* e, int count, size_t lds, hipStream_t st, const EvPair& ev, const double* xs, const int* list,

@@ -30,10 +30,10 @@ static void free_all(lqrrt_engine* e) {
     if (e->d_cand2) (void)hipFree(e->d_cand2);
     if (e->d_flags2) (void)hipFree(e->d_flags2);
     void* ptrs[] = {e->d_vps, e->d_obs, e->d_oc, e->d_og, e->d_ogc, e->d_cell_start, e->d_cell_items, e->d_S, e->tv.state, e->tv.trig, e->tv.werr, e->tv.K, e->tv.pID, e->tv.elen,
-                    e->tv.xedge, e->tv.uedge, e->tv.ignore, e->d_rec, e->d_pcost, e->d_M,
-                    e->d_pidx, e->d_par_done, e->d_par_want, e->d_list,
-                    e->d_changed, e->d_stale, e->d_need, e->d_summary, e->d_pool, e->d_pool_trig, e->d_pool_S, e->d_QR, e->d_Sop, e->d_cand, e->d_flags,
-                    e->d_M2, e->d_lf[0], e->d_lf[1], e->d_par2, e->d_stale2, e->d_changed2, e->d_head2, e->d_rctl, e->d_rank,
+                    e->tv.xedge, e->tv.uedge, e->tv.ignore, e->d_rec, e->d_pcost, e->d_round,
+                    e->d_pidx, e->d_par_want, e->d_list,
+                    e->d_need, e->d_summary, e->d_pool, e->d_pool_trig, e->d_pool_S, e->d_QR, e->d_Sop, e->d_cand, e->d_flags,
+                    e->d_head2, e->d_rank,
                     e->d_blk, e->d_blk_cursor, e->d_ref, e->d_ref_key, e->d_refm, e->d_con};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -151,22 +151,24 @@ extern "C" int lqrrt_engine_create(const lqrrt_system_desc* sys, int device, int
     const size_t pw = (size_t)lqrrt_engine::MAXCH * e->maxW;
     if (!rc) rc = dalloc(&e->d_pcost, 2 * pw);               // the tree scans' partial minima: [pw] 16-byte words (kernels.hpp Part)
     if (!rc) rc = dalloc(&e->d_pidx, pw);                    // (in-wave scans of waves > 256 samples: costs in d_pcost, ids here)
-    if (!rc) rc = dalloc(&e->d_M, (size_t)lqrrt_engine::MATRIX_MAX_W * lqrrt_engine::MATRIX_MAX_W);
-    if (!rc) rc = dalloc(&e->d_par_done, (size_t)e->maxW);
+    // the round block: in-wave matrices, the double-buffered per-sample arrays and the rounds' control block in one allocation
+    static_assert(ROUND_MATRIX_W == lqrrt_engine::MATRIX_MAX_W, "round_layout is written for the engine's matrix limit");
+    const RoundLayout rl = round_layout(e->maxW);
+    if (!rc) rc = dalloc(&e->d_round, (size_t)rl.bytes);
+    if (!rc) {
+        unsigned char* b = e->d_round;
+        e->d_rctl = (int*)(b + rl.ctl);
+        e->d_M = (double*)(b + rl.M[0]); e->d_M2 = (double*)(b + rl.M[1]);
+        e->d_lf[0] = (int*)(b + rl.lf[0]); e->d_lf[1] = (int*)(b + rl.lf[1]);
+        e->d_par_done = (int*)(b + rl.par[0]); e->d_par2 = (int*)(b + rl.par[1]);
+        e->d_stale = b + rl.stale[0]; e->d_stale2 = b + rl.stale[1];
+        e->d_changed = b + rl.changed[0]; e->d_changed2 = b + rl.changed[1];
+    }
     if (!rc) rc = dalloc(&e->d_par_want, (size_t)e->maxW);
     if (!rc) rc = dalloc(&e->d_list, (size_t)e->maxW);
-    if (!rc) rc = dalloc(&e->d_changed, (size_t)e->maxW);
-    if (!rc) rc = dalloc(&e->d_stale, (size_t)e->maxW);
     if (!rc) rc = dalloc(&e->d_need, (size_t)e->maxW);
     if (!rc) rc = dalloc(&e->d_summary, (size_t)4);
-    if (!rc) rc = dalloc(&e->d_M2, (size_t)lqrrt_engine::MATRIX_MAX_W * lqrrt_engine::MATRIX_MAX_W);
-    if (!rc) rc = dalloc(&e->d_lf[0], (size_t)2 * e->maxW);
-    if (!rc) rc = dalloc(&e->d_lf[1], (size_t)2 * e->maxW);
-    if (!rc) rc = dalloc(&e->d_par2, (size_t)e->maxW);
-    if (!rc) rc = dalloc(&e->d_stale2, (size_t)e->maxW);
-    if (!rc) rc = dalloc(&e->d_changed2, (size_t)e->maxW);
     if (!rc) rc = dalloc(&e->d_head2, (size_t)lqrrt_engine::MATRIX_MAX_W * (n + 2 * nw + m * n));
-    if (!rc) rc = dalloc(&e->d_rctl, (size_t)16);
     if (!rc) rc = dalloc(&e->d_rank, (size_t)e->maxW);
     if (!rc && hipMemset(e->d_rctl, 0, sizeof(int) * 16) != hipSuccess) rc = fail(LQRRT_E_HIP, "hipMemset failed");
     const unsigned hflags = hipHostMallocMapped | hipHostMallocCoherent;

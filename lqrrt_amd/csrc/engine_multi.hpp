@@ -43,13 +43,9 @@ static void multi_build_proto(lqrrt_engine* e, EngineProto& p) {
     f.M = e->d_M;
     f.lf0 = e->d_lf[0]; f.round_ctl = e->d_rctl;
     RoundArgs& ra = p.ra;
-    ra.M[0] = e->d_M; ra.M[1] = e->d_M2;
-    ra.lf[0] = e->d_lf[0]; ra.lf[1] = e->d_lf[1];
-    ra.par[0] = e->d_par_done; ra.par[1] = e->d_par2;
-    ra.stale[0] = e->d_stale; ra.stale[1] = e->d_stale2;
-    ra.changed[0] = e->d_changed; ra.changed[1] = e->d_changed2;
+    ra.blk = e->d_round; ra.maxW = e->maxW;
     ra.head2 = e->d_head2;
-    ra.ctl = e->d_rctl; ra.rank = e->d_rank;
+    ra.rank = e->d_rank;
     ra.host_ctrl = e->h_round_dev; ra.host_summary = e->h_round_dev + 8;
     ra.fx = e->fix;
 }

@@ -114,7 +114,10 @@ struct lqrrt_engine {
     int* h_summary_dev = nullptr; // device address of h_summary
     int* h_rank = nullptr;        // pinned + mapped [maxW]
     int* h_rank_dev = nullptr;
-    // fused repair rounds (kernels.hpp RoundArgs): second parity of the double-buffered wave state, control block
+    // fused repair rounds (kernels.hpp RoundArgs): second parity of the double-buffered wave state, control block.  d_M, d_par_done,
+    // d_changed, d_stale above and everything up to d_rctl below (d_head2 excepted) point into ONE allocation, d_round, laid out by
+    // round_layout(maxW) (rounds.hpp): the rounds address it from its base.
+    unsigned char* d_round = nullptr;
     double* d_M2 = nullptr;
     int* d_lf[2] = {nullptr, nullptr};
     int* d_par2 = nullptr;

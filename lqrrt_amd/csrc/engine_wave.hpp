@@ -416,13 +416,9 @@ static int commit_impl(lqrrt_engine* e, int W, int64_t max_commit, int64_t node_
         ra.on = 1; ra.W = W; ra.base = e->N;
         ra.max_commit = max_commit;
         ra.room = node_limit >= 0 ? node_limit + 1 - (int64_t)e->N : -1;
-        ra.M[0] = e->d_M; ra.M[1] = e->d_M2;
-        ra.lf[0] = e->d_lf[0]; ra.lf[1] = e->d_lf[1];
-        ra.par[0] = e->d_par_done; ra.par[1] = e->d_par2;
-        ra.stale[0] = e->d_stale; ra.stale[1] = e->d_stale2;
-        ra.changed[0] = e->d_changed; ra.changed[1] = e->d_changed2;
+        ra.blk = e->d_round; ra.maxW = e->maxW;
         ra.head2 = e->d_head2;
-        ra.ctl = e->d_rctl; ra.rank = e->d_rank;
+        ra.rank = e->d_rank;
         ra.host_ctrl = e->h_round_dev; ra.host_summary = e->h_round_dev + 8;
         ra.fx = e->fix;
         SteerFuse qf = rf;
@@ -458,10 +454,10 @@ static int commit_impl(lqrrt_engine* e, int W, int64_t max_commit, int64_t node_
                 HIPCHK(hipStreamSynchronize(st));                  // (the counts arrive while re-steering workgroups still run)
                 std::vector<int> lf(2 * W), pr(W);
                 std::vector<unsigned char> ch(W), sl(W);
-                HIPCHK(hipMemcpy(lf.data(), ra.lf[nx], sizeof(int) * 2 * W, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(pr.data(), ra.par[nx], sizeof(int) * W, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(ch.data(), ra.changed[nx], W, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemcpy(sl.data(), ra.stale[nx], W, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(lf.data(), e->d_lf[nx], sizeof(int) * 2 * W, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(pr.data(), nx ? e->d_par2 : e->d_par_done, sizeof(int) * W, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(ch.data(), nx ? e->d_changed2 : e->d_changed, W, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(sl.data(), nx ? e->d_stale2 : e->d_stale, W, hipMemcpyDeviceToHost));
                 fprintf(stderr, "[roundstate N=%d W=%d r=%d]", e->N, W, r);
                 for (int t = 0; t < W; ++t) fprintf(stderr, " %d:%d:%d:%d:%d", pr[t], lf[2 * t], lf[2 * t + 1] & 1, (int)(ch[t] & 1), (int)sl[t]);
                 fprintf(stderr, "\n");

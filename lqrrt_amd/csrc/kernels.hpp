@@ -102,9 +102,10 @@ struct RecLayout {
     int R, off_cost, off_parent, off_len, off_flags, off_xend, off_trig, off_K, off_xseq, off_useq;
 };
 
+constexpr int REC_OFF_COST = 0, REC_OFF_PARENT = 1;      // the same for every system: k_steer's entry does not wait for the layout to ask
 __host__ __device__ inline RecLayout make_layout(int n, int m, int nw, int H) {
     RecLayout L;
-    L.off_cost = 0; L.off_parent = 1; L.off_len = 2; L.off_flags = 3;
+    L.off_cost = REC_OFF_COST; L.off_parent = REC_OFF_PARENT; L.off_len = 2; L.off_flags = 3;
     L.off_xend = 4;
     L.off_trig = L.off_xend + n;
     L.off_K = L.off_trig + 2 * nw;

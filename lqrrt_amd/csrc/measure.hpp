@@ -1,6 +1,6 @@
 // Measurement scaffolding of the kernels, in one place: nothing in here is part of the product build.
 //   -DSTEER_TIMING   device timestamps in k_steer (tools/steer_phases_bench.py, tools/ablate_steer.py): phase stamps of workgroup 0,
-//                    per-step phase sums of the rollout loop, prologue / loop / kernel time of full-horizon rollouts, a histogram of
+//                    per-step phase sums of the rollout loop, entry / prologue / loop / kernel time of full-horizon rollouts, a histogram of
 //                    their loop times; read back through the lqrrt_debug_* entry points at the end of engine.hip
 //   -DABL_NOFEAS / -DABL_NORUDDER / -DABL_NOTRIG   ablations of a rollout step (tools/ablate_steer.py): the collision sweep, the
 //                    heading torque, the elementary functions replaced by something free -- the RESULTS are wrong, the timing
@@ -18,6 +18,14 @@ __device__ unsigned long long g_step_acc[8];        // per-phase ticks of the ro
 __device__ unsigned long long g_loop_hist[32];      // loop time of full-horizon rollouts, 2 us buckets
 __device__ unsigned long long g_blk_acc[8];         // full-horizon rollouts: sum kernel time, sum loop time, count, max kernel, max loop, sum / max prologue
 __device__ unsigned long long g_pro_acc[16];        // prologue of rolling workgroups: [mode*5 + {to the parent choice, parent loads, to barrier S, count}]
+__device__ unsigned long long g_ent_acc[8];         // entry of rolling workgroups: [mode*2 + {until the first argument is in a register, until the first batch of loads is back}]
+// the first argument-dependent wait made explicit (the value has to be in a scalar register here) / the first batch of vector loads drained
+#define STEER_ARG_WAIT(x) asm volatile("" :: "s"(x))
+#define STEER_LOADS_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define BLK_VAR(v) [[maybe_unused]] unsigned long long v = 0
+#define BLK_SET(v) v = wall_clock64()
+#define STEER_T_ENTRY(mode, t0, ta, tb) do { if (threadIdx.x == 0) {                                                          \
+        atomicAdd(&g_ent_acc[(mode) * 2 + 0], (ta) - (t0)); atomicAdd(&g_ent_acc[(mode) * 2 + 1], (tb) - (ta)); } } while (0)
 #define STEER_TS(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_steer_ts[i] = wall_clock64(); } while (0)
 #define BLK_T(v) const unsigned long long v = wall_clock64()
 #define STEP_TS(v) const unsigned long long v = wall_clock64()
@@ -35,6 +43,11 @@ __device__ unsigned long long g_pro_acc[16];        // prologue of rolling workg
         const unsigned long long t3__ = wall_clock64();                                                                       \
         atomicAdd(&g_blk_acc[0], t3__ - (t0)); atomicMax(&g_blk_acc[3], t3__ - (t0)); } } while (0)
 #else
+#define STEER_ARG_WAIT(x) do {} while (0)
+#define STEER_LOADS_WAIT() do {} while (0)
+#define BLK_VAR(v) [[maybe_unused]] const unsigned long long v = 0
+#define BLK_SET(v) do {} while (0)
+#define STEER_T_ENTRY(mode, t0, ta, tb) do { (void)(t0); (void)(ta); (void)(tb); } while (0)
 #define STEER_TS(i) do {} while (0)
 #define BLK_T(v) const unsigned long long v = 0
 #define STEP_TS(v) do {} while (0)

@@ -57,14 +57,13 @@ __global__ __launch_bounds__(64 * NWF) void k_steer_multi(ProtoTable pt, SteerMu
     }
     SteerFuse f = p.f;
     f.W = d.W; f.xtrig = d.xtrig;
-    const int* par = nullptr;
     int rd_on = 0;
     if (d.mode == MULTI_SPECULATE) {
         f.n_chunks = d.n_chunks; f.nv.count = d.N;
-        par = f.par_out;
     } else {
         f.n_chunks = 0; f.M = nullptr;
         rd_on = 1;
     }
-    steer_body<S, DENSE, NWF, false>(p.P, p.g, p.r, p.tv, p.rec, p.L, d.xs, nullptr, 0, par, nullptr, f, p.ra, rd_on, d.round, d.W, d.base, d.seq, d.max_commit, d.room, bid);
+    steer_body<S, DENSE, NWF, false>(p.P, p.g, p.r, p.tv, p.rec, p.L, p.L.R, d.xs, nullptr, 0, p.f.par_out, nullptr, 0, f.part, f.n_chunks, f, p.ra,
+                                     RoundBlk{p.ra.blk, p.ra.maxW}, rd_on, d.round, d.W, d.base, d.seq, d.max_commit, d.room, bid);
 }

@@ -12,14 +12,48 @@
 // double-buffered by round parity: round r reads [r & 1] and writes [1 - (r & 1)], unchanged samples copy theirs.  The
 // launch that follows a converged round finds the flag set and is the append (tree.py:77-96): one kernel boundary per
 // round instead of two, none for the commit.  Same decisions as k_decide by construction; lqrrt_wave_commit chooses.
+//
+// The double-buffered arrays and the rounds' control block live in ONE allocation, the round block, whose offsets follow from the
+// engine's wave capacity alone (round_layout): a launch addresses all of them from one base pointer and maxW, two of the few
+// arguments that fit the registers a dispatch preloads (k_steer's hot header, steer.hpp), instead of ten pointers that a round
+// would first have to fetch from its argument block.  Offsets in bytes:
+//   ctl        int[16]: packed {ticket, n_list, n_defer} x 2 (64-bit each), -, -, converged[2], C, acc
+//   M[p]       in-wave cost matrices [W][W], W <= ROUND_MATRIX_W
+//   lf[p]      {len, flags} per sample
+//   par[p]     parent in use per sample
+//   stale[p]   one byte per sample
+//   changed[p] bit 0: re-steered in the round that wrote it; bit 1: which copy of the record HEAD is current
+// (p = round parity.  The host keeps pointers into the block -- d_M, d_par_done, d_changed, d_stale are parity 0 -- for the
+//  launches that are not rounds.)
+constexpr int ROUND_MATRIX_W = 256;      // largest wave with an in-wave cost matrix (lqrrt_engine::MATRIX_MAX_W)
+struct RoundLayout { long long ctl, M[2], lf[2], par[2], stale[2], changed[2], bytes; };
+__host__ __device__ constexpr long long round_mw8(int maxW) { return ((long long)maxW + 7) & ~7ll; }    // per-sample arrays end on 8 bytes
+__host__ __device__ constexpr long long round_off_M(int p) { return 64 + (long long)p * ROUND_MATRIX_W * ROUND_MATRIX_W * 8; }
+__host__ __device__ constexpr long long round_off_lf(int maxW, int p) { return round_off_M(2) + (long long)p * 8 * round_mw8(maxW); }
+__host__ __device__ constexpr long long round_off_par(int maxW, int p) { return round_off_lf(maxW, 2) + (long long)p * 4 * round_mw8(maxW); }
+__host__ __device__ constexpr long long round_off_stale(int maxW, int p) { return round_off_par(maxW, 2) + (long long)p * round_mw8(maxW); }
+__host__ __device__ constexpr long long round_off_changed(int maxW, int p) { return round_off_stale(maxW, 2) + (long long)p * round_mw8(maxW); }
+__host__ __device__ constexpr RoundLayout round_layout(int maxW) {
+    return RoundLayout{0, {round_off_M(0), round_off_M(1)}, {round_off_lf(maxW, 0), round_off_lf(maxW, 1)},
+                       {round_off_par(maxW, 0), round_off_par(maxW, 1)}, {round_off_stale(maxW, 0), round_off_stale(maxW, 1)},
+                       {round_off_changed(maxW, 0), round_off_changed(maxW, 1)}, round_off_changed(maxW, 2)};
+}
+static_assert(round_layout(1).bytes == round_off_M(2) + 28 * 8 && round_layout(65).lf[1] % 8 == 0 && round_layout(65).par[1] % 4 == 0 &&
+              round_layout(63).stale[0] == round_layout(63).par[1] + 4 * 64, "round block layout (both compilation passes)");
+// a launch's view of the block: base pointer, the capacity the offsets follow from
+struct RoundBlk {
+    unsigned char* b; int maxW;
+    __device__ __forceinline__ int* ctl() const { return (int*)b; }
+    __device__ __forceinline__ double* M(int p) const { return (double*)(b + round_off_M(p)); }
+    __device__ __forceinline__ int* lf(int p) const { return (int*)(b + round_off_lf(maxW, p)); }
+    __device__ __forceinline__ int* par(int p) const { return (int*)(b + round_off_par(maxW, p)); }
+    __device__ __forceinline__ unsigned char* stale(int p) const { return b + round_off_stale(maxW, p); }
+    __device__ __forceinline__ unsigned char* changed(int p) const { return b + round_off_changed(maxW, p); }
+};
 struct RoundArgs {
-    int on, round, W, base, seq, pad0;
+    int on, round, W, base, seq, maxW;   // maxW: the capacity the round block was laid out for
     long long max_commit, room;          // commit limits of lqrrt_wave_commit (room < 0: no node limit)
-    double* M[2];                        // in-wave cost matrices [W][W]
-    int* lf[2];                          // {len, flags} per sample
-    int* par[2];                         // parent in use per sample
-    unsigned char* stale[2];
-    unsigned char* changed[2];           // bit 0: re-steered in the round that wrote it; bit 1: which copy of the record HEAD is current
+    unsigned char* blk;                  // the round block (layout above)
     // Second copy of every record's head (xend | trig | K, contiguous like in the record), [W][n + 2 NW + m n].  A sample that re-steers
     // writes its new head into the copy that is NOT current and flips bit 1 of its `changed` byte for the next round, so that a
     // workgroup which reads another sample's head during a launch (load_parent) always reads what the PREVIOUS launch left: since
@@ -27,7 +61,6 @@ struct RoundArgs {
     // head let it read a half-written state (same final tree -- the torn rollout is always redone -- but the counts of
     // rounds and re-steers, which feed the wave-size controller and with it the all-gather sizes of a sharded world, depended on timing).
     double* head2;
-    int* ctl;                            // device: packed {ticket, n_list, n_defer} x 2 (64-bit each), -, -, converged[2], C, acc
     int* rank;                           // device [W]: accepted samples before t (written at convergence)
     int* host_ctrl;                      // pinned: as k_decide's ctrl
     int* host_summary;                   // pinned: len, flags, parent per sample (converged round only)
@@ -40,7 +73,7 @@ struct RoundArgs {
 };
 // (What changes from launch to launch in RoundArgs -- on, round, W, base, seq, max_commit, room -- reaches steer_body / close_round as
 //  scalars `rd_*`: the one-engine kernel passes its arguments' fields, the multi-engine kernel its per-engine slot, while the rest of
-//  RoundArgs stays where it is; a local COPY of RoundArgs would live in scratch, its two-element arrays are indexed by the round's parity.)
+//  RoundArgs stays where it is.  k_steer takes on / round / W from its hot header, which the host fills from these fields.)
 // header of sample s of a gathered wave: the record up to the edges + one word, where its edge lies in its block's tail
 __device__ __forceinline__ const double* gathered_header(const RoundArgs& ra, int s) {
     return ra.gblk + (size_t)(s / ra.gper) * ra.gstride + (size_t)(s % ra.gper) * ra.ghd;
@@ -57,10 +90,10 @@ constexpr unsigned long long RC_ONE_LIST = 1ull << 16, RC_ONE_DEFER = 1ull << 32
 // The last workgroup to add its share to the round's word closes the round: counts to the host and, in a converged round,
 // ranks and the committed prefix for the append.  One wavefront (the helpers wait at barrier S or are gone): no workgroup
 // barrier in here.  (A function, not a lambda: a closure that is not scalarised costs the kernel a stack frame.)
-__device__ __forceinline__ void close_round(const RoundArgs& ra, const int rd_on, const int rd_round, const int rd_W, const int rd_base, const int rd_seq, const long long rd_max_commit, const long long rd_room, const RecLayout& L, int lane, unsigned long long round_before, unsigned long long round_share) {
+__device__ __forceinline__ void close_round(const RoundArgs& ra, const RoundBlk& rb, const int rd_on, const int rd_round, const int rd_W, const int rd_base, const int rd_seq, const long long rd_max_commit, const long long rd_room, const RecLayout& L, int lane, unsigned long long round_before, unsigned long long round_share) {
     const int cur = rd_round & 1, nxt = cur ^ 1;
     const bool g0 = ra.gblk != nullptr;
-    unsigned long long* word_r = (unsigned long long*)(ra.ctl + RC_PACK) + cur;
+    unsigned long long* word_r = (unsigned long long*)(rb.ctl() + RC_PACK) + cur;
     const unsigned long long before_me = ((unsigned long long)(unsigned)__shfl((int)(round_before >> 32), 0) << 32) |
                                          (unsigned)__shfl((int)round_before, 0);
     if ((int)(before_me & 0xffffu) == rd_W - 1) {
@@ -71,7 +104,7 @@ __device__ __forceinline__ void close_round(const RoundArgs& ra, const int rd_on
             // commit rules of lqrrt_wave_commit (planner.py:311 node limit, :270 the wave ends at a goal hit), on the
             // final records: accepted-before counts, committed prefix C.  (Nobody re-steers: this round's buffers
             // will be copies of the previous round's, which the kernel boundary has already published.)
-            const int* lfn = ra.lf[cur];
+            const int* lfn = rb.lf(cur);
             int before = 0, first_hit = rd_W, t_room = rd_W;
             for (int c0 = 0; c0 < rd_W; c0 += 64) {
                 const int tt = c0 + lane;
@@ -84,7 +117,7 @@ __device__ __forceinline__ void close_round(const RoundArgs& ra, const int rd_on
                 if (in) {
                     ra.rank[tt] = mine;
                     ra.host_summary[tt] = len; ra.host_summary[rd_W + tt] = flg;
-                    ra.host_summary[2 * rd_W + tt] = g0 ? (int)hh[L.off_parent] : ra.par[cur][tt];
+                    ra.host_summary[2 * rd_W + tt] = g0 ? (int)hh[L.off_parent] : rb.par(cur)[tt];
                     if (a && (flg & 1)) first_hit = min(first_hit, tt);
                     if (rd_room >= 0 && (long long)mine >= rd_room) t_room = min(t_room, tt);
                 }
@@ -102,13 +135,13 @@ __device__ __forceinline__ void close_round(const RoundArgs& ra, const int rd_on
             const int C = (int)(Cl < 0 ? 0 : Cl);
             // ranks of samples at or beyond C are never used by the append (parents point backwards)
             if (lane == 0) {
-                ra.ctl[RC_C] = C;
-                ra.ctl[RC_CONV + nxt] = 1;
+                rb.ctl()[RC_C] = C;
+                rb.ctl()[RC_CONV + nxt] = 1;
                 ra.host_ctrl[0] = first_hit < rd_W ? first_hit : rd_W - 1;
             }
         }
         // (a gathered wave has no speculative launch of its own that clears the flags of the wave before it)
-        if (g0 && lane == 0) { ra.ctl[RC_CONV + cur] = 0; if (!converged) ra.ctl[RC_CONV + nxt] = 0; }
+        if (g0 && lane == 0) { rb.ctl()[RC_CONV + cur] = 0; if (!converged) rb.ctl()[RC_CONV + nxt] = 0; }
         if (lane == 0) *word_r = 0ull;                                                          // for round + 2
         // the summary (all lanes' stores, pinned host memory) before the word that announces it
         if (converged) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __threadfence_system(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }

@@ -143,26 +143,48 @@ __device__ __forceinline__ bool rollout_check(const double* Pl, const Geo& g, co
     return stop;
 }
 
+// An argument of the cold part read HERE: the compiler may not lift the load out of the branch that asks for it (it does, for
+// loads it can prove safe, and a load in flight at the kernel's entry is a wait where the entry modes' paths join).
+template <class T> __device__ __forceinline__ T read_here(const T& x) { const T* p = &x; asm volatile("" : "+s"(p)); return *p; }
+enum { STEER_HOT_LIST = 1, STEER_HOT_COUNT = 2, STEER_HOT_GATHERED = 4 };     // k_steer's `hot`: list / list_count / ra.gblk is set
+constexpr int STEER_HOT_DWORDS = 14, STEER_HOT_BYTES = 4 * STEER_HOT_DWORDS;   // k_steer's hot header (at its definition below)
+
 template <class S, int DENSE, int NWF, bool KERNARG_TOUCH>
 __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const Res& r, const TreeView& tv, double* __restrict__ rec,
-                                           const RecLayout& L, const double* __restrict__ xs,
-                                           const int* __restrict__ list, const int lo,
-                                           const int* __restrict__ par, const int* __restrict__ list_count,
-                                           const SteerFuse& f, const RoundArgs& ra, const int rd_on, const int rd_round, const int rd_W, const int rd_base, const int rd_seq, const long long rd_max_commit, const long long rd_room, const int bid) {
+                                           const RecLayout& L, const int rec_R, const double* __restrict__ xs,
+                                           const int* const& list, const int lo,
+                                           const int* const& par, const int* const& list_count, const int hot,
+                                           const Part* __restrict__ part, const int n_chunks,
+                                           const SteerFuse& f, const RoundArgs& ra, const RoundBlk rb, const int rd_on, const int rd_round, const int rd_W, const int rd_base, const int rd_seq, const long long rd_max_commit, const long long rd_room, const int bid) {
     // (round 4: Riccati-gain systems run the fused rounds too -- their in-wave matrix holds the cost under the S about each sample)
+    // (list, par, list_count by reference: k_steer hands over fields of the cold part, read where the code asks for them)
     const bool ron = rd_on != 0;
+    // which of the launch's optional pointers are there, from the hot header: asking the pointers themselves (list, list_count,
+    // ra.gblk) would be a wait for the cold part of the argument block in front of the first loads
+    const bool has_list = (hot & STEER_HOT_LIST) != 0, has_count = (hot & STEER_HOT_COUNT) != 0, gath = (hot & STEER_HOT_GATHERED) != 0;
     // list mode with a device-side count: the launch is enqueued before the host knows how many samples
     // k_decide listed, so surplus workgroups simply leave (and a converged round costs one empty launch)
-    if (list_count && bid + lo >= list_count[0]) return;
+    int t = lo + bid;
+    if (has_list) {
+        if (has_count && bid + lo >= read_here(list_count)[0]) return;
+        t = read_here(list)[bid + (has_count ? lo : 0)];
+        // (the list's loads are waited for in here: left pending, they would make the other entry modes wait where the paths join)
+        t = __builtin_amdgcn_readfirstlane(t);
+    }
 #ifndef LQRRT_NO_KERNARG_TOUCH
     if constexpr (KERNARG_TOUCH) {
         // The argument block is ~2 KB (31 cache lines) that no cache holds when a launch starts, and most of it is read
         // lazily, at the point of use, by scalar loads on the critical path (~1 us each on a miss).  One vector load per line
         // up front brings the whole block into this XCD's L2 while the first real loads are in flight anyway.
-        const volatile int* ka = (const volatile int*)__builtin_amdgcn_kernarg_segment_ptr();
+        // Nobody waits for the touch: a `volatile` load is followed by a wait for it (the memory model orders volatile accesses), a
+        // full round trip in front of the first loads that the hot header exists to remove -- a relaxed atomic load is kept by the
+        // compiler as well and ordered against nothing.  (A global, not a flat load: a flat one would also count as an LDS access
+        // and hold up the first scalar wait behind it.)
+        typedef __attribute__((address_space(1))) int global_int;
+        global_int* ka = (global_int*)__builtin_amdgcn_kernarg_segment_ptr();
         constexpr int KA_LINES = (int)((sizeof(Params) + sizeof(Geo) + sizeof(Res) + sizeof(TreeView) + sizeof(RecLayout) +
-                                        sizeof(SteerFuse) + sizeof(RoundArgs) + 40) / 64);       // (rounded down: never past the block)
-        if ((int)(threadIdx.x & 63) < KA_LINES) (void)ka[(threadIdx.x & 63) * 16];
+                                        sizeof(SteerFuse) + sizeof(RoundArgs) + STEER_HOT_BYTES + 24) / 64);       // (rounded down: never past the block)
+        if ((int)(threadIdx.x & 63) < KA_LINES) (void)__hip_atomic_load(ka + (threadIdx.x & 63) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #endif
     STEER_TS(0);
@@ -180,15 +202,20 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
     static_assert(!has_dare_gain<S>::value || NWF == 1 || NWF == 4, "Riccati systems: one wavefront, or four that share the gain");
     constexpr bool PLAIN2 = NWF == 2 && !is_packed<S>::value;
     extern __shared__ double hist[];
-    double* hx = hist;
-    double* hu = hist + (size_t)r.H * S::N;
+    // (where the edge history lies follows from the horizon and the geometry's size, both in the cold part of the argument block:
+    //  every wavefront works it out when it gets there, the main one behind its first batch of loads -- set_hist)
+    double *hx = nullptr, *hu = nullptr, *htr = nullptr;
     const int lane = threadIdx.x & 63;
     __shared__ double Pl[MAXP];
     __shared__ double tol_l[MAXN], glo_l[MAXN], ghi_l[MAXN];
     __shared__ double node_l[MAXN + 4 + MAXM * MAXN];        // the new node on its way out: xend | trig | K
     __shared__ GainLds<S> gl_lds;                            // work space of a Riccati gain (empty for analytic gains)
     __shared__ DuoLds duo;
-    double* htr = hist + (size_t)r.H * (S::N + S::M) + geo_lds_doubles(g);   // DUO: cos/sin of every recorded state
+    auto set_hist = [&]() {
+        hx = hist;
+        hu = hist + (size_t)r.H * S::N;
+        htr = hist + (size_t)r.H * (S::N + S::M) + geo_lds_doubles(g);       // DUO: cos/sin of every recorded state
+    };
     constexpr int PKN = S::N + 2 * S::NW;                                    // plain two-wavefront packet: offset of e
     // Chain rollout (three wavefronts, every system with the heading-torque pieces; round 4).  With the torque of a moving boat
     // down to one atan2 the dependency chain of a step, x_k -> torque -> x_k+1, is ~230 instructions INCLUDING erf, u = K e and
@@ -207,7 +234,8 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
     if constexpr (CH) {
         if (threadIdx.x >= 128) {
             // ---------------- checking wavefront
-            if (ron && !ra.gblk && ra.ctl[RC_CONV + (rd_round & 1)]) return;           // this launch is the append: nothing to roll out
+            if (ron && !gath && rb.ctl()[RC_CONV + (rd_round & 1)]) return;           // this launch is the append: nothing to roll out
+            set_hist();
             for (int i = lane; i < MAXP; i += 64) Pl[i] = P.p[i];
             if (lane < MAXN) { tol_l[lane] = r.tol[lane]; glo_l[lane] = r.goal_lo[lane]; ghi_l[lane] = r.goal_hi[lane]; }
             const GeoL gl = stage_geo(g, hist + (size_t)r.H * (S::N + S::M), lane, 64);
@@ -243,7 +271,7 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         }
         if (threadIdx.x >= 64) {
             // ---------------- heading wavefront: what step p + 1 needs and only depends on two components of x_p
-            if (ron && !ra.gblk && ra.ctl[RC_CONV + (rd_round & 1)]) return;
+            if (ron && !gath && rb.ctl()[RC_CONV + (rd_round & 1)]) return;
             __syncthreads();                                                // S
             if (!duo.go) return;
             const double tt0 = duo.tt[0], tt1 = duo.tt[1];
@@ -265,7 +293,8 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
     if constexpr (PLAIN2) {
         if (threadIdx.x >= 64) {
             // ---------------- checking wavefront of the plain two-wavefront rollout
-            if (ron && !ra.gblk && ra.ctl[RC_CONV + (rd_round & 1)]) return;           // this launch is the append: nothing to roll out
+            if (ron && !gath && rb.ctl()[RC_CONV + (rd_round & 1)]) return;           // this launch is the append: nothing to roll out
+            set_hist();
             for (int i = lane; i < MAXP; i += 64) Pl[i] = P.p[i];
             if (lane < MAXN) { tol_l[lane] = r.tol[lane]; glo_l[lane] = r.goal_lo[lane]; ghi_l[lane] = r.goal_hi[lane]; }
             const GeoL gl = stage_geo(g, hist + (size_t)r.H * (S::N + S::M), lane, 64);
@@ -293,7 +322,8 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
     if constexpr (NWF == 2 && !PLAIN2) {
         if (threadIdx.x >= 64) {
             // ---------------- helper wavefront
-            if (ron && !ra.gblk && ra.ctl[RC_CONV + (rd_round & 1)]) return;           // this launch is the append: nothing to roll out
+            if (ron && !gath && rb.ctl()[RC_CONV + (rd_round & 1)]) return;           // this launch is the append: nothing to roll out
+            set_hist();
             for (int i = lane; i < MAXP; i += 64) Pl[i] = P.p[i];
             if (lane < MAXN) { tol_l[lane] = r.tol[lane]; glo_l[lane] = r.goal_lo[lane]; ghi_l[lane] = r.goal_hi[lane]; }
             const GeoL gl = stage_geo(g, hist + (size_t)r.H * (S::N + S::M), lane, 64);
@@ -359,18 +389,27 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             }
         }
     }
-    const int t = list ? list[bid + (list_count ? lo : 0)] : lo + bid;
-    double* my = rec + (size_t)t * L.R;
+    double* my = rec + (size_t)t * rec_R;
 
     double x[S::N], K[S::M * S::N], trig[2 * S::NW + 1], xt[S::N], ttrig[2 * S::NW + 1];
 #pragma unroll
     for (int d = 0; d < S::N; ++d) xt[d] = xs[(size_t)t * S::N + d];
-    if (f.xtrig) {
+    // (the scheduler would lift the block's loads of cold arguments above these, and the spills of their values -- the kernel
+    //  lives at the SGPR limit -- are a wait for the argument block in front of the sample's loads)
+    __builtin_amdgcn_sched_barrier(0);
+    STEER_ARG_WAIT(xs);
+    BLK_T(blk_ta);
+    BLK_VAR(blk_tb);
+    // cos/sin of the target.  f.xtrig is in the cold part of the argument block, so the question is asked behind the first batch
+    // of loads of every entry mode (which only needs the hot header), not in front of it: the answer flies with the parent's state.
+    auto load_ttrig = [&]() {
+        if (f.xtrig) {
 #pragma unroll
-        for (int j = 0; j < 2 * S::NW; ++j) ttrig[j] = f.xtrig[(size_t)t * (2 * S::NW) + j];
-    } else {
-        trig_of<S>(xt, ttrig);
-    }
+            for (int j = 0; j < 2 * S::NW; ++j) ttrig[j] = f.xtrig[(size_t)t * (2 * S::NW) + j];
+        } else {
+            trig_of<S>(xt, ttrig);
+        }
+    };
     bool parent_loaded = false;
     constexpr int HD = S::N + 2 * S::NW + S::M * S::N;            // a record's head: xend | trig | K
     int psel = 0;                                                  // fused rounds: which copy of an in-wave parent's head is current
@@ -386,9 +425,9 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         } else {
             // (round 0 of a gathered wave: the in-wave parent's record is being unpacked by ITS workgroup right now -- read the header;
             //  any other fused round: the copy of the head that the previous launch left current, see RoundArgs::head2)
-            const double* hp = (ron && ra.gblk) ? gathered_header(ra, ~p) + L.off_xend
+            const double* hp = (ron && gath) ? gathered_header(ra, ~p) + L.off_xend
                              : (ron && psel)    ? ra.head2 + (size_t)(~p) * HD
-                                                : rec + (size_t)(~p) * L.R + L.off_xend;
+                                                : rec + (size_t)(~p) * rec_R + L.off_xend;
 #pragma unroll
             for (int d = 0; d < S::N; ++d) x[d] = hp[d];
 #pragma unroll
@@ -400,20 +439,20 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
     int pref;
     unsigned long long round_share = 1ull;                        // fused round: this workgroup's contribution to the round's word
     unsigned long long round_before = 0;                          // (lane 0) the round's word as this workgroup's atomic found it
-    if (f.n_chunks > 0) {
+    if (n_chunks > 0) {
         // nearest node of this sample from the scan's partial minima (see k_nn_reduce for the rules)
         double b = INFINITY;
         int bi = -1;
-        const Part* pp = f.part + (size_t)bid * f.n_chunks;
+        const Part* pp = part + (size_t)bid * n_chunks;
         // (eight loads per lane in flight: the partials were written by other workgroups a moment ago, every access is a
         // ~1 us round trip, and the conditional update below keeps the compiler from overlapping the iterations itself)
-        for (int c0 = lane; c0 < f.n_chunks; c0 += 512) {
+        for (int c0 = lane; c0 < n_chunks; c0 += 512) {
             double v[8];
             int vi[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int c = c0 + 64 * q;
-                const bool in = c < f.n_chunks;
+                const bool in = c < n_chunks;
                 Part pm;
                 pm.c = INFINITY; pm.i = -1;
                 if (in) pm = pp[c];                                  // one 16-byte load per partial
@@ -424,7 +463,10 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             for (int q = 0; q < 8; ++q)                              // ascending chunks per lane, as before
                 if (vi[q] >= 0 && (bi < 0 || v[q] < b)) { b = v[q]; bi = vi[q]; }
         }
+        STEER_LOADS_WAIT();
+        BLK_SET(blk_tb);
         lexmin_wave(b, bi);
+        load_ttrig();
         const bool fallback = bi < 0 && f.nv.ignore != nullptr;
         if (fallback) {
             for (int i = lane; i < f.nv.count; i += 64) {
@@ -440,8 +482,8 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             lexmin_wave(b, bi);
         }
         if (lane == 0) {
-            my[L.off_cost] = fallback ? INFINITY : b;
-            my[L.off_parent] = (double)bi;
+            my[REC_OFF_COST] = fallback ? INFINITY : b;
+            my[REC_OFF_PARENT] = (double)bi;
             f.par_out[t] = bi; f.changed[t] = 0; f.stale[t] = 0;
             if (f.round_ctl && bid == 0) {
 #pragma unroll
@@ -451,7 +493,7 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         pref = bi;
     } else if (ron) {
         const int cur = rd_round & 1, nxt = cur ^ 1;
-        const bool g0 = ra.gblk != nullptr;                       // round 0 of a gathered wave: decide from the all-gather blocks
+        const bool g0 = gath;                       // round 0 of a gathered wave: decide from the all-gather blocks
         // cost of the end state in header h for sample u (the arithmetic of the row epilogue / k_wave_rows); +inf: no node
         auto hcost = [&](const double* h, int u) -> double {
             if (!((int)h[L.off_len] > 0)) return INFINITY;
@@ -470,7 +512,7 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             return quad_cost<S, DENSE>(e, f.Sd + (size_t)u * f.s_stride);
         };
         // batch A: everything the decision needs that only depends on t (issued before the flag is even tested)
-        const int conv_flag = g0 ? 0 : ra.ctl[RC_CONV + cur];
+        const int conv_flag = g0 ? 0 : rb.ctl()[RC_CONV + cur];
         int lf_len[4], lf_flg[4];
         unsigned char chg[4];
         double colv[4];
@@ -499,28 +541,31 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
                 chg[i] = 0;
                 colv[i] = (tt < t) ? hcost(h, t) : INFINITY;
             }
-            csnap_t = ht[L.off_cost];
-            psnap_t = (int)ht[L.off_parent];
+            csnap_t = ht[REC_OFF_COST];
+            psnap_t = (int)ht[REC_OFF_PARENT];
             par_t = psnap_t;
             // an edge that did not fit its rank's tail: re-steered in this round, by its owner too (replicated rounds)
             stale_t = ((int)ht[L.off_len] > 0 && (int)ht[L.off_xseq] < 0) ? 1 : 0;
         } else {
-            const int* lfc = ra.lf[cur];
-            const double* Mc = ra.M[cur];
+            const int* lfc = rb.lf(cur);
+            const double* Mc = rb.M(cur);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int tt = lane + 64 * i;
                 const bool in = tt < rd_W;
                 lf_len[i] = in ? lfc[2 * tt] : 0;
                 lf_flg[i] = in ? lfc[2 * tt + 1] : 0;
-                chg[i] = in ? ra.changed[cur][tt] : 0;
+                chg[i] = in ? rb.changed(cur)[tt] : 0;
                 colv[i] = (tt < t) ? Mc[(size_t)tt * rd_W + t] : INFINITY;
             }
-            csnap_t = rec[(size_t)t * L.R + L.off_cost];
-            psnap_t = (int)rec[(size_t)t * L.R + L.off_parent];
-            par_t = ra.par[cur][t];
-            stale_t = ra.stale[cur][t];
+            csnap_t = rec[(size_t)t * rec_R + REC_OFF_COST];
+            psnap_t = (int)rec[(size_t)t * rec_R + REC_OFF_PARENT];
+            par_t = rb.par(cur)[t];
+            stale_t = rb.stale(cur)[t];
         }
+        load_ttrig();
+        STEER_LOADS_WAIT();
+        BLK_SET(blk_tb);
         auto flags_of = [&](int idx) -> int {                      // the `changed` byte [cur][idx] from the lanes' prefetched bytes
             int v = 0;
 #pragma unroll
@@ -533,8 +578,8 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         if (conv_flag) {
             // the previous round converged: this launch is the commit.  Sample t's record becomes tree node
             // base + rank[t] if it lies in the committed prefix (tree.py:77-96; what k_append does).
-            const int C = ra.ctl[RC_C];
-            const int len = ra.lf[cur][2 * t];
+            const int C = rb.ctl()[RC_C];
+            const int len = rb.lf(cur)[2 * t];
             if (t < C && len > 0) {
                 const int id = rd_base + ra.rank[t];
                 const double* hd = sel_t ? ra.head2 + (size_t)t * HD : my + L.off_xend;
@@ -548,7 +593,7 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
                 }
                 for (int q = lane; q < S::M * S::N; q += 64) tv.K[(size_t)id * S::M * S::N + q] = hd[S::N + 2 * S::NW + q];
                 if (lane == 0) {
-                    const int p = ra.par[cur][t];
+                    const int p = rb.par(cur)[t];
                     tv.pID[id] = p >= 0 ? p : rd_base + ra.rank[~p];
                     tv.elen[id] = len;
                 }
@@ -584,16 +629,16 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             if (need && want < 0) {
                 // the in-wave parent's own decision, evaluated here instead of waited for: redone this round -> defer
                 const int sn = ~want;                              // (sn < t <= hz)
-                const double* Mc = ra.M[cur];
+                const double* Mc = rb.M(cur);
                 const double* hs = g0 ? gathered_header(ra, sn) : nullptr;
                 double cs[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     cs[i] = (lane + 64 * i < sn) ? (g0 ? hcost(gathered_header(ra, lane + 64 * i), sn) : Mc[(size_t)(lane + 64 * i) * rd_W + sn]) : INFINITY;
-                const double csnap_s = g0 ? hs[L.off_cost] : rec[(size_t)sn * L.R + L.off_cost];
-                const int psnap_s = g0 ? (int)hs[L.off_parent] : (int)rec[(size_t)sn * L.R + L.off_parent];
-                const int par_s = g0 ? psnap_s : ra.par[cur][sn];
-                const int stale_s = g0 ? (((int)hs[L.off_len] > 0 && (int)hs[L.off_xseq] < 0) ? 1 : 0) : ra.stale[cur][sn];
+                const double csnap_s = g0 ? hs[REC_OFF_COST] : rec[(size_t)sn * rec_R + REC_OFF_COST];
+                const int psnap_s = g0 ? (int)hs[REC_OFF_PARENT] : (int)rec[(size_t)sn * rec_R + REC_OFF_PARENT];
+                const int par_s = g0 ? psnap_s : rb.par(cur)[sn];
+                const int stale_s = g0 ? (((int)hs[L.off_len] > 0 && (int)hs[L.off_xseq] < 0) ? 1 : 0) : rb.stale(cur)[sn];
                 double ws = INFINITY;
                 int ss = -1;
 #pragma unroll
@@ -634,9 +679,9 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         // a new head goes to the copy that is not current (round 0 of a gathered wave: nobody reads the records, in place)
         head_out = g0 ? 0 : (redo ? sel_t ^ 1 : sel_t);
         if (lane == 0) {
-            ra.par[nxt][t] = redo ? want : par_t;
-            ra.stale[nxt][t] = redo ? 0 : ((need && defer) || mark_stale ? 1 : stale_t);
-            ra.changed[nxt][t] = (unsigned char)((redo ? 1 : 0) | (head_out << 1));
+            rb.par(nxt)[t] = redo ? want : par_t;
+            rb.stale(nxt)[t] = redo ? 0 : ((need && defer) || mark_stale ? 1 : stale_t);
+            rb.changed(nxt)[t] = (unsigned char)((redo ? 1 : 0) | (head_out << 1));
         }
         if (redo) round_share += RC_ONE_LIST;
         else if (need) round_share += RC_ONE_DEFER;
@@ -646,7 +691,7 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             // the last one -- in a converged round that is ~5 us into the launch, so the host hears about the wave while the
             // launch is still running; one that re-steers looks after its rollout, when the answer has long arrived: no
             // workgroup ends with an atomic round trip across the chip.
-            unsigned long long* word_r = (unsigned long long*)(ra.ctl + RC_PACK) + cur;
+            unsigned long long* word_r = (unsigned long long*)(rb.ctl() + RC_PACK) + cur;
             if (threadIdx.x == 0) round_before = __hip_atomic_fetch_add(word_r, round_share, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // (the look at what came back happens at the end of this function, which a workgroup that stands reaches at once)
         }
@@ -654,20 +699,24 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
             // nothing to recompute: this sample's row and len/flags move on unchanged (gathered round 0: they are made here)
             if (g0) {
                 const double* ht = gathered_header(ra, t);
-                for (int u = t + 1 + lane; u < rd_W; u += 64) ra.M[nxt][(size_t)t * rd_W + u] = hcost(ht, u);
-                if (lane < 2) ra.lf[nxt][2 * t + lane] = (int)ht[lane == 0 ? L.off_len : L.off_flags];
+                for (int u = t + 1 + lane; u < rd_W; u += 64) rb.M(nxt)[(size_t)t * rd_W + u] = hcost(ht, u);
+                if (lane < 2) rb.lf(nxt)[2 * t + lane] = (int)ht[lane == 0 ? L.off_len : L.off_flags];
             } else {
-                for (int u = t + 1 + lane; u < rd_W; u += 64) ra.M[nxt][(size_t)t * rd_W + u] = ra.M[cur][(size_t)t * rd_W + u];
-                if (lane < 2) ra.lf[nxt][2 * t + lane] = ra.lf[cur][2 * t + lane];
+                for (int u = t + 1 + lane; u < rd_W; u += 64) rb.M(nxt)[(size_t)t * rd_W + u] = rb.M(cur)[(size_t)t * rd_W + u];
+                if (lane < 2) rb.lf(nxt)[2 * t + lane] = rb.lf(cur)[2 * t + lane];
             }
             pref = 0x7fffffff;                                  // (marker: skip the rollout, go to the ticket)
         } else {
             pref = want;
         }
     } else {
-        pref = par[t];
+        pref = read_here(par)[t];
+        load_ttrig();
+        STEER_LOADS_WAIT();
+        BLK_SET(blk_tb);
     }
     BLK_T(blk_tp);
+    set_hist();
     const bool round_skip = ron && pref == 0x7fffffff;
     if constexpr (DUO) {
         if (round_skip) { duo.go = 0; __syncthreads(); }         // S: the helper leaves
@@ -688,7 +737,8 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         duo.tt[0] = ttrig[0]; duo.tt[1] = ttrig[1];
         __syncthreads();                                             // S
         BLK_T(blk_t1);
-        STEER_T_PROLOGUE(f.n_chunks > 0 ? 0 : (ron ? 1 : 2), blk_t0, blk_tp, blk_tq, blk_t1);
+        STEER_T_PROLOGUE(n_chunks > 0 ? 0 : (ron ? 1 : 2), blk_t0, blk_tp, blk_tq, blk_t1);
+        STEER_T_ENTRY(n_chunks > 0 ? 0 : (ron ? 1 : 2), blk_t0, blk_ta, blk_tb);
         // model constants in registers for the whole rollout: every index below is a compile-time constant, so the copy is
         // scalarised and only what the step uses stays live (loads from LDS inside the loop could not be hoisted across the barrier)
         double Pc[S::NP];
@@ -928,11 +978,11 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
         //        bits 8.. = number of completed steps (for the horizon_iters replay on the host)
         const int fw = flags | (grew ? 2 : 0) | (steps << 8);
         my[L.off_flags] = (double)fw;
-        int* lfo = ron ? ra.lf[(rd_round & 1) ^ 1] : f.lf0;
+        int* lfo = ron ? rb.lf((rd_round & 1) ^ 1) : f.lf0;
         if (lfo) { lfo[2 * t] = cnt; lfo[2 * t + 1] = fw; }
     }
     STEER_TS(4);
-    double* Mout = ron ? ra.M[(rd_round & 1) ^ 1] : f.M;
+    double* Mout = ron ? rb.M((rd_round & 1) ^ 1) : f.M;
     const int Wm = ron ? rd_W : f.W;
     if (Mout) {
         // row t of the in-wave cost matrix: cost of this record's end state for every later sample u (the
@@ -977,16 +1027,44 @@ __device__ __forceinline__ void steer_body(const Params& P, const Geo& g, const 
     STEER_TS(5);
     STEER_T_KERNEL(steps, blk_t0);
     }   // !round_skip
-    if (ron && threadIdx.x < 64) close_round(ra, rd_on, rd_round, rd_W, rd_base, rd_seq, rd_max_commit, rd_room, L, lane, round_before, round_share);   // (the workgroup's first wavefront holds the ticket)
+    if (ron && threadIdx.x < 64) close_round(ra, rb, rd_on, rd_round, rd_W, rd_base, rd_seq, rd_max_commit, rd_room, L, lane, round_before, round_share);   // (the workgroup's first wavefront holds the ticket)
 }
 
+// k_steer's arguments.  What the first batch of loads of an entry mode needs comes first, as plain pointers and scalars: the
+// HOT HEADER, 14 dwords -- as many as the dispatcher can place in scalar registers before a wavefront starts (kernarg preload:
+// 16 user SGPRs minus the argument-segment pointer; the build asks for it, tools/engine_flags.py, and the compiler stops at the
+// first by-value struct).  A launch then issues its first loads at once instead of behind a ~1 us scalar fetch of its own argument
+// block; the cold rest (~2 KB of structs) arrives, touched at entry, while those loads are in flight.
+//   speculative launch:  xs, rec, part, n_chunks, lo
+//   fused round:         rnd (the round, -1: no round), wm (W | maxW << 16), blk (rounds.hpp round_layout), rec, rec_R
+//   every mode:          hot (STEER_HOT_*: which optional pointers of the cold part are set)
+// -DLQRRT_NO_KERNARG_PRELOAD (A/B builds) puts the header behind the structs, where nothing of it is preloaded.
+#define STEER_HOT_PARAMS double* __restrict__ rec, const double* __restrict__ xs, const Part* __restrict__ part, unsigned char* blk, \
+                         int lo, int n_chunks, int wm, int rnd, int rec_R, int hot
+#define STEER_COLD_PARAMS Params P, Geo g, Res r, TreeView tv, RecLayout L, const int* list, const int* par, const int* list_count, \
+                          SteerFuse f, RoundArgs ra
+// The cold part in the order the kernel declares it: with the preload the body reads it through the argument-segment pointer, not
+// through the parameters.  The compiler loads every PARAMETER it needs in the kernel's entry block, and with this kernel at the
+// SGPR limit it spills what it loaded there at once -- a wait for the whole argument block in front of the first loads, which
+// the hot header exists to remove; reads through a pointer stay where the code asks for them.
+struct SteerCold { Params P; Geo g; Res r; TreeView tv; RecLayout L; const int* list; const int* par; const int* list_count; SteerFuse f; RoundArgs ra; };
 template <class S, int DENSE, int NWF>
-__global__ __launch_bounds__(64 * NWF) void k_steer(Params P, Geo g, Res r, TreeView tv, double* __restrict__ rec,
-                                              RecLayout L, const double* __restrict__ xs,
-                                              const int* __restrict__ list, int lo,
-                                              const int* __restrict__ par, const int* __restrict__ list_count,
-                                              SteerFuse f, RoundArgs ra) {
-    steer_body<S, DENSE, NWF, true>(P, g, r, tv, rec, L, xs, list, lo, par, list_count, f, ra, ra.on, ra.round, ra.W, ra.base, ra.seq, ra.max_commit, ra.room,
-                              (int)blockIdx.x);
+#ifndef LQRRT_NO_KERNARG_PRELOAD
+__global__ __launch_bounds__(64 * NWF) void k_steer(STEER_HOT_PARAMS, SteerCold) {
+    typedef const __attribute__((address_space(4))) SteerCold* cold_ptr;
+    static_assert(STEER_HOT_BYTES % alignof(SteerCold) == 0, "the cold part follows the hot header without padding");
+    auto kp = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + STEER_HOT_BYTES;
+    asm volatile("" : "+s"(kp));
+    const SteerCold& c = *(const SteerCold*)(cold_ptr)kp;
+    steer_body<S, DENSE, NWF, true>(c.P, c.g, c.r, c.tv, rec, c.L, rec_R, xs, c.list, lo, c.par, c.list_count, hot, part, n_chunks, c.f, c.ra,
+                                    RoundBlk{blk, wm >> 16}, rnd >= 0 ? 1 : 0, rnd, wm & 0xffff, c.ra.base, c.ra.seq, c.ra.max_commit, c.ra.room,
+                                    (int)blockIdx.x);
 }
-
+#else
+__global__ __launch_bounds__(64 * NWF) void k_steer(STEER_COLD_PARAMS, STEER_HOT_PARAMS) {
+    steer_body<S, DENSE, NWF, true>(P, g, r, tv, rec, L, rec_R, xs, list, lo, par, list_count, hot, part, n_chunks, f, ra, RoundBlk{blk, wm >> 16},
+                                    rnd >= 0 ? 1 : 0, rnd, wm & 0xffff, ra.base, ra.seq, ra.max_commit, ra.room, (int)blockIdx.x);
+}
+#endif
+#undef STEER_HOT_PARAMS
+#undef STEER_COLD_PARAMS

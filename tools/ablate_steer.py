@@ -7,8 +7,9 @@ sys.path.insert(0, ROOT)
 import numpy as np
 variant = sys.argv[1] if len(sys.argv) > 1 else ''
 so = '/tmp/liblqrrt_%s.so' % (variant.replace(',', '_') or 'base')
-cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-I', os.path.join(ROOT, 'include'),
-       os.path.join(ROOT, 'lqrrt_amd/csrc/engine.hip'), '-o', so] + ['-D' + v for v in variant.split(',') if v]
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import engine_flags
+cmd = engine_flags.shared_library_command(ROOT, so, ['-D' + v for v in variant.split(',') if v])
 subprocess.check_call(cmd)
 import lqrrt_amd._native as nat
 nat.LIB_PATH = so

@@ -12,15 +12,16 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import engine_flags
+HIPCC = engine_flags.HIPCC
 
 
 def build(header, out):
     header = os.path.abspath(header)
     csrc = os.path.join(ROOT, "lqrrt_amd", "csrc")
     define = "-DLQRRT_USER_SYSTEM=\"%s\"" % header
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-           define, os.path.join(csrc, "engine.hip"), "-o", os.path.abspath(out)]
+    cmd = engine_flags.shared_library_command(ROOT, os.path.abspath(out), [define])
     # By-products for the CPU tests that pin registers / occupancy / ISA (tests/test_abi_cpu.py via tools/kernel_resources.py): the
     # resource-usage remarks of THIS compile, and the device assembly from a compile that runs beside it -- so that those tests
     # read a cache instead of compiling engine.hip two more times (~3 min each).

@@ -11,8 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 so = os.environ.get("DARE_TIMING_LIB", "/tmp/liblqrrt_DARE_TIMING.so")
 if not os.path.exists(so):
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "lqrrt_amd/csrc/engine.hip"), "-o", so, "-DDARE_TIMING"])
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import engine_flags
+    subprocess.check_call(engine_flags.shared_library_command(ROOT, so, ["-DDARE_TIMING"]))
 import lqrrt_amd._native as nat
 nat.LIB_PATH = so
 import numpy as np

@@ -9,7 +9,9 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import engine_flags                                             # the flags of the library that runs: what is reported here is its code
+HIPCC = engine_flags.HIPCC
 
 
 REMARK_FLAG = "-Rpass-analysis=kernel-resource-usage"
@@ -24,7 +26,7 @@ def source_key(extra=()):
     files = []
     for d in (os.path.join(ROOT, "lqrrt_amd", "csrc"), os.path.join(ROOT, "include")):
         files += [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith((".hip", ".hpp", ".def", ".h"))]
-    for x in extra:
+    for x in list(engine_flags.ENGINE_FLAGS) + list(extra):
         h.update(x.encode())
         m = re.match(r'-DLQRRT_USER_SYSTEM="?([^"]+)"?$', x)
         if m:
@@ -68,8 +70,7 @@ def remarks(extra=()):
     if os.path.exists(path):
         return open(path).read()
     src = os.path.join(ROOT, "lqrrt_amd", "csrc", "engine.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", src, "-o", "/dev/null",
-           REMARK_FLAG] + list(extra)
+    cmd = [HIPCC] + engine_flags.ENGINE_FLAGS + ["-c", src, "-o", "/dev/null", REMARK_FLAG] + list(extra)
     text = subprocess.run(cmd, capture_output=True, text=True, cwd=os.path.dirname(src)).stderr
     if "Function Name" in text:
         store("remarks", extra, text)
@@ -78,7 +79,7 @@ def remarks(extra=()):
 
 def device_asm_command(out, extra=()):
     src = os.path.join(ROOT, "lqrrt_amd", "csrc", "engine.hip")
-    return [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-S", "--cuda-device-only", src, "-o", out] + list(extra)
+    return [HIPCC] + engine_flags.ENGINE_FLAGS + ["-S", "--cuda-device-only", src, "-o", out] + list(extra)
 
 
 def device_asm(extra=()):

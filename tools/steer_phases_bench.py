@@ -8,10 +8,13 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-so = "/tmp/liblqrrt_STEER_TIMING.so"
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                       "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "lqrrt_amd/csrc/engine.hip"), "-o", so, "-DSTEER_TIMING"]
-                      + ["-D" + d for d in os.environ.get("STEER_DEFINES", "").split(",") if d])
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import engine_flags
+# STEER_TIMING_LIB: a library built with -DSTEER_TIMING beforehand (hipcc cross-compiles without a GPU) instead of a build here
+so = os.environ.get("STEER_TIMING_LIB", "/tmp/liblqrrt_STEER_TIMING.so")
+if "STEER_TIMING_LIB" not in os.environ or not os.path.exists(so):
+    subprocess.check_call(engine_flags.shared_library_command(
+        ROOT, so, ["-DSTEER_TIMING"] + ["-D" + d for d in os.environ.get("STEER_DEFINES", "").split(",") if d]))
 if len(sys.argv) > 1:
     os.environ["LQRRT_STEER_WAVEFRONTS"] = sys.argv[1]
 import lqrrt_amd._native as nat
@@ -45,6 +48,15 @@ for mode, name in enumerate(("speculative launch", "fused repair round (re-steer
     c = max(1, q[mode * 5 + 3])
     print("prologue, %-40s %6d workgroups: to the parent choice %.2f us | parent loads %.2f | until the helpers' barrier %.2f" % (
         name, q[mode * 5 + 3], q[mode * 5 + 0] * 0.01 / c, q[mode * 5 + 1] * 0.01 / c, q[mode * 5 + 2] * 0.01 / c))
+# the entry of those workgroups (tools/README.md; profiles/steer_entry_phases.txt): until the first argument is in a scalar register,
+# until the first batch of loads is back, then decision + dependent batch (parent loads) and the LDS set-up to barrier S
+en = (C.c_ulonglong * 8)()
+nat.lib().lqrrt_debug_ent_acc(en)
+for mode, name in enumerate(("speculative launch", "fused repair round (re-steered samples)", "listed re-steer")):
+    c = max(1, q[mode * 5 + 3])
+    a, b = en[mode * 2] * 0.01 / c, en[mode * 2 + 1] * 0.01 / c
+    print("entry,    %-40s %6d workgroups: arguments %.2f us | first batch %.2f | decision + dependent batch %.2f | LDS set-up to barrier S %.2f" % (
+        name, q[mode * 5 + 3], a, b, (q[mode * 5 + 0] + q[mode * 5 + 1]) * 0.01 / c - a - b, q[mode * 5 + 2] * 0.01 / c))
 h = (C.c_ulonglong * 32)()
 nat.lib().lqrrt_debug_loop_hist(h)
 print("loop time of full-horizon rollouts, 2 us buckets:", " ".join("%d-%d:%d" % (2 * i, 2 * i + 2, h[i]) for i in range(32) if h[i]))
