@@ -176,10 +176,11 @@ extern "C" int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, i
 
 // --------------------------------------------------------------------------------------------
 // Several trees per call: lqrrt_connect_search_multi / lqrrt_connect_commit_multi (connect_goals), on engine_refine.hpp's multi
-// path: its engine-list check, chunks, scratch (d_refm: not part of the footprint), prototypes, keys and guard.  A search's image per
-// chunk: the keys, then a ConnectDesc per engine, then every engine's depth table and id list; one launch (connect.hpp
-// k_connect_search_multi).  The commit IS refine_commit_multi_run: per winner the one-node plan [v] with the cost prefix
-// [depth[v]], i = j = 0.
+// path: its engine-list check and its two runners, which own the chunks, the scratch (d_refm: not part of the footprint), the
+// prototypes, the keys, the guard and the one synchronise.  The search states its hooks: a ConnectDesc per engine, behind it every
+// engine's depth table and id list (MultiCands), one launch (connect.hpp k_connect_search_multi), a key's decoding.  The commit
+// states none: it IS the refinement's, multi_commit_run with RefineCommitMulti -- per winner the one-node plan [v] with the cost
+// prefix [depth[v]], i = j = 0.
 
 // what the two calls check alike, for every engine
 static int connect_multi_check(lqrrt_engine** engines, int n, const int32_t* tries, const int32_t* horizons) {
@@ -194,79 +195,75 @@ static int multi_id_list(const int32_t* const* nodes, const int32_t* counts, int
     return 0;
 }
 
-static int connect_search_multi_run(lqrrt_engine** engines, int n, const int32_t* const* nodes, const std::vector<int>& counts,
-                                    const std::vector<std::vector<int>>& depths, const int32_t* tries, const int32_t* horizons,
-                                    const int64_t* incumbents, int64_t* cost, int32_t* node_out, hipStream_t st) {
-    const std::vector<long long> cands(counts.begin(), counts.end());   // (an empty id list: no launch, no winner)
-    std::vector<MultiChunk> chunks = multi_chunks(cands);
-    StreamDrain drain(st);
-    for (MultiChunk& c : chunks) {
-        const int m = (int)c.members.size();
-        Carve carve;
-        carve(sizeof(unsigned long long) * m);                  // the keys
-        const size_t o_desc = carve(sizeof(ConnectDesc) * m);
-        std::vector<size_t> o_depth((size_t)m), o_ids((size_t)m);
-        for (int q = 0; q < m; ++q) {
-            const int k = c.members[q];
-            o_depth[q] = carve(sizeof(int) * depths[k].size());
-            o_ids[q] = carve(nodes && nodes[k] ? sizeof(int) * (size_t)counts[k] : 0);
-        }
-        c.img.assign(carve.off, 0);
-        char* d_img = nullptr;
-        TRY(refine_multi_scratch(engines[c.first], carve.off, &d_img));
-        ConnectDesc* hd = (ConnectDesc*)(c.img.data() + o_desc);
-        for (int q = 0; q < m; ++q) {
-            const int k = c.members[q];
-            const bool listed = nodes && nodes[k];
-            ((unsigned long long*)c.img.data())[q] = incumbent_key(incumbents[k]);   // (incumbent, node 0)
-            memcpy(c.img.data() + o_depth[q], depths[k].data(), sizeof(int) * depths[k].size());
-            if (listed) memcpy(c.img.data() + o_ids[q], nodes[k], sizeof(int) * (size_t)counts[k]);
-            connect_fill_args(engines[k], (const int*)(d_img + o_depth[q]), listed ? (const int*)(d_img + o_ids[q]) : nullptr, counts[k],
-                              tries[k], horizons[k], &hd[q].a);
-            hd[q].best = (unsigned long long*)d_img + q;
-        }
-        ProtoTable pt;
-        size_t lds = 0;
-        TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
-        RetainGrid gr;
-        const unsigned grid = multi_grid(c, cands, gr);
-        drain.arm();
-        HIPCHK(hipMemcpyAsync(d_img, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
-        DISPATCH(engines[0], hipLaunchKernelGGL((k_connect_search_multi<S>), dim3(grid), dim3(64), lds, st, pt,
-                                                (const ConnectDesc*)(d_img + o_desc), gr));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c.img.data(), d_img, sizeof(unsigned long long) * m, hipMemcpyDeviceToHost, st));
+// What a search over the nodes of several trees (connect, via, reach) keeps per engine of its call -- the id list (null: every
+// node), the candidate count, the depth table -- and the one staging of a member's depth table and optional id list into a chunk's
+// image.
+struct MultiCands {
+    std::vector<const int32_t*> ids;
+    std::vector<int> counts;                                    // (an empty id list: no launch, no winner)
+    std::vector<std::vector<int>> depths;
+    explicit MultiCands(int n) : ids((size_t)n, nullptr), counts((size_t)n, 0), depths((size_t)n) {}
+    struct At { size_t depth, ids; };
+    At carve(int k, Carve& carve) const {
+        const size_t o_depth = carve(sizeof(int) * depths[k].size());
+        return {o_depth, carve(ids[k] ? sizeof(int) * (size_t)counts[k] : 0)};
     }
-    std::vector<unsigned long long> keys;
-    TRY(multi_search_keys(chunks, n, incumbents, st, drain, keys));
-    for (int k = 0; k < n; ++k) {
-        if (keys[k] == incumbent_key(incumbents[k])) continue;
-        cost[k] = (int64_t)(keys[k] >> 32);
-        node_out[k] = (int32_t)(keys[k] & 0xffffffffull);
+    // engine k's table and list into c's image, and depth / nodes / count of its argument block
+    template <class Args>
+    void stage(int k, const At& at, MultiChunk& c, Args* a) const {
+        memcpy(c.img.data() + at.depth, depths[k].data(), sizeof(int) * depths[k].size());
+        if (ids[k]) memcpy(c.img.data() + at.ids, ids[k], sizeof(int) * (size_t)counts[k]);
+        a->depth = (const int*)(c.dev + at.depth);
+        a->nodes = ids[k] ? (const int*)(c.dev + at.ids) : nullptr;
+        a->count = counts[k];
     }
-    return 0;
-}
+};
+
+// the search's hooks (engine_refine.hpp: multi_search_run)
+struct ConnectSearchMulti {
+    typedef ConnectDesc Desc;
+    typedef MultiCands::At Part;
+    const MultiCands& x;
+    lqrrt_engine** engines;
+    const int32_t* tries; const int32_t* horizons; const int64_t* incumbents; int64_t* cost; int32_t* node_out;
+    long long groups(int k) const { return x.counts[k]; }
+    int keys(int) const { return 1; }
+    int64_t incumbent(int k, int) const { return incumbents[k]; }   // (incumbent, node 0)
+    Part carve(const MultiChunk& c, size_t q, Carve& carve) const { return x.carve(c.members[q], carve); }
+    void fill(MultiChunk& c, size_t q, const std::vector<Part>& at, ConnectDesc* d) const {
+        const int k = c.members[q];
+        connect_fill_args(engines[k], nullptr, nullptr, 0, tries[k], horizons[k], &d->a);
+        x.stage(k, at[q], c, &d->a);
+        d->best = c.keys_of(c.dev, q);
+    }
+    template <class S>
+    static void launch(unsigned grid, size_t lds, hipStream_t st, const ProtoTable& pt, const ConnectDesc* ds, const RetainGrid& gr) {
+        hipLaunchKernelGGL((k_connect_search_multi<S>), dim3(grid), dim3(64), lds, st, pt, ds, gr);
+    }
+    void won(int k, int, unsigned long long key) const {
+        cost[k] = (int64_t)(key >> 32);
+        node_out[k] = (int32_t)(key & 0xffffffffull);
+    }
+};
 
 extern "C" int lqrrt_connect_search_multi(lqrrt_engine** engines, int n, const int32_t* const* nodes, const int32_t* counts,
                                           const int32_t* goal_tries, const int32_t* horizon_iters, const int64_t* incumbents,
                                           int64_t* cost_out, int32_t* node_out, void* stream) {
     TRY(connect_multi_check(engines, n, goal_tries, horizon_iters));
     if (!incumbents || !cost_out || !node_out) return fail(LQRRT_E_ARG, "null argument");
-    std::vector<int> cnt((size_t)n);
-    std::vector<std::vector<int>> depths((size_t)n);
+    MultiCands x(n);
     for (int k = 0; k < n; ++k) {
         lqrrt_engine* e = engines[k];
-        const int32_t* ids = nullptr;
         TRY(incumbent_check(incumbents[k], k));
-        TRY(multi_id_list(nodes, counts, k, &ids, &cnt[k]));
-        TRY(connect_candidates_check(e, ids, &cnt[k], k));
-        depths[k].assign((size_t)e->N, 0);
-        TRY(connect_depths(e, goal_tries[k], horizon_iters[k], depths[k].data()));
+        TRY(multi_id_list(nodes, counts, k, &x.ids[k], &x.counts[k]));
+        TRY(connect_candidates_check(e, x.ids[k], &x.counts[k], k));
+        x.depths[k].assign((size_t)e->N, 0);
+        TRY(connect_depths(e, goal_tries[k], horizon_iters[k], x.depths[k].data()));
     }
     TRY(use_device(engines[0]));
     for (int k = 0; k < n; ++k) { cost_out[k] = incumbents[k]; node_out[k] = -1; }
-    return connect_search_multi_run(engines, n, nodes, cnt, depths, goal_tries, horizon_iters, incumbents, cost_out, node_out,
-                                    (hipStream_t)stream);
+    return multi_search_run(engines, n, horizon_iters, (hipStream_t)stream,
+                            ConnectSearchMulti{x, engines, goal_tries, horizon_iters, incumbents, cost_out, node_out});
 }
 
 extern "C" int lqrrt_connect_commit_multi(lqrrt_engine** engines, int n, const int32_t* nodes, const int32_t* goal_tries,
@@ -287,6 +284,6 @@ extern "C" int lqrrt_connect_commit_multi(lqrrt_engine** engines, int n, const i
         ij[k] = 0;
     }
     TRY(use_device(engines[0]));
-    return refine_commit_multi_run(engines, n, bufs, ones.data(), goal_tries, horizon_iters, ij.data(), ij.data(), ids_out, counts_out,
-                                   (hipStream_t)stream);
+    return multi_commit_run(engines, n, horizon_iters, ids_out, counts_out, (hipStream_t)stream,
+                            RefineCommitMulti{{engines, bufs, ones.data(), goal_tries, horizon_iters}, ij.data(), ij.data()});
 }

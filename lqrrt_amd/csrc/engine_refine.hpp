@@ -5,9 +5,9 @@
 // (engine_reach.hpp), goal chains through waypoints (engine_connect_via.hpp, engine_connect_via_multi.hpp) -- that search candidates
 // in one launch and replay the winner in another.  What their host sides share is stated once, here where its first user is: the
 // rules of an argument (incumbent_check, goal_fill), the end of a one-engine commit (commit_finish), the guard of a call's host
-// images (StreamDrain), and for the calls that take several engines the engine-list check, the chunks, their images' layout and
-// what is read back from them (MultiChunk and the multi_* functions).  The kernel launched, its descriptor and the decoding of a
-// key are each caller's own.
+// images (StreamDrain), and for the calls that take several engines the engine-list check and the two runners that string a call's
+// chunks together (multi_search_run, multi_commit_run, with MultiChunk and the multi_* functions).  The kernel launched, its
+// descriptor, the tables behind it and the decoding of a key are each caller's own: its hooks.
 // --------------------------------------------------------------------------------------------
 
 // " (engine k)" behind a message of a call for several engines; nothing behind that of a one-engine call (k < 0)
@@ -220,8 +220,11 @@ struct MultiChunk {
     int first = 0;                        // the engine (index into the call) whose scratch holds the image
     std::vector<int> members;             // indices (into the call) of the engines that take part in the launch
     std::vector<char> img;                // host image of the scratch
+    char* dev = nullptr;                  // the scratch: where the image goes on the device
+    std::vector<size_t> key_at;           // search, per member: its first key (the keys lie at the image's head, member by member)
     size_t o_out = 0, o_lens = 0, back = 0;   // commit: the outputs [4] per member, the edge lengths, the bytes that come back
     std::vector<size_t> lens_at;          // commit, per member: its first edge length (ints from o_lens)
+    unsigned long long* keys_of(char* image, size_t q) const { return (unsigned long long*)image + key_at[q]; }
     int* out_of(char* image, size_t q) const { return (int*)(image + o_out) + 4 * q; }
     int* lens_of(char* image, size_t q) const { return (int*)(image + o_lens) + lens_at[q]; }
 };
@@ -302,19 +305,6 @@ static unsigned multi_grid(const MultiChunk& c, const std::vector<long long>& gr
     return retain_grid(counts, gr);
 }
 
-// A search's image starts with one best key per member.  Waits for the call's chunks (its one synchronise) and returns every
-// engine's key: what its launch left, or its incumbent's where the engine took part in none.
-static int multi_search_keys(const std::vector<MultiChunk>& chunks, int n, const int64_t* incumbents, hipStream_t st, StreamDrain& drain,
-                             std::vector<unsigned long long>& keys) {
-    HIPCHK(hipStreamSynchronize(st));
-    drain.disarm();
-    keys.resize((size_t)n);
-    for (int k = 0; k < n; ++k) keys[k] = incumbent_key(incumbents[k]);
-    for (const MultiChunk& c : chunks)
-        for (size_t q = 0; q < c.members.size(); ++q) keys[c.members[q]] = ((const unsigned long long*)c.img.data())[q];
-    return 0;
-}
-
 // A commit's image starts with what comes back: out[4] per member (commit_finish's three, padded), then room[k] edge lengths for
 // every member k.
 static void multi_commit_head(MultiChunk& c, const std::vector<int>& room, Carve& carve) {
@@ -341,6 +331,110 @@ static void multi_commit_adopt(lqrrt_engine** engines, std::vector<MultiChunk>& 
         }
 }
 
+// The two runners: the launches of a checked call, chunk by chunk, and the call's one synchronise.  They own the order that makes
+// a call safe -- the image is allocated before the guard is armed, the guard is armed before the first copy and disarmed only
+// after the synchronise that succeeded -- and a call states in a hooks object h only what is its own:
+//   h.Desc, h.Part           the descriptor per member; where a member's tables lie in the image
+//   h.carve(c, q, carve)     carves the tables of member q of chunk c behind the descriptors, in the image's order
+//   h.fill(c, q, at, d)      fills member q's descriptor d and its tables in c.img (at: what carve returned, per member); device
+//                            addresses are those of c.dev
+//   h.launch<S>(...)         the one launch, which names the call's kernel
+// and, a search: h.groups(k), the workgroups of engine k (0: it takes part in no launch); h.keys(k), its number of keys, and
+// h.incumbent(k, t), the cost behind key t, which starts as incumbent_key of it; h.won(k, t, key) for every key that a launch
+// replaced.  A commit: h.winner(k), whether engine k has a candidate to replay (one workgroup each), with h.room(k) edges at most
+// below node h.parent(k); the runner sets out / lens / base of its descriptor.
+template <class H>
+static int multi_search_run(lqrrt_engine** engines, int n, const int32_t* horizons, hipStream_t st, const H& h) {
+    typedef typename H::Desc Desc;
+    std::vector<long long> groups((size_t)n);
+    for (int k = 0; k < n; ++k) groups[k] = h.groups(k);
+    std::vector<MultiChunk> chunks = multi_chunks(groups);
+    StreamDrain drain(st);
+    for (MultiChunk& c : chunks) {
+        const size_t m = c.members.size();
+        size_t n_keys = 0;
+        for (int k : c.members) { c.key_at.push_back(n_keys); n_keys += (size_t)h.keys(k); }
+        Carve carve;
+        carve(sizeof(unsigned long long) * n_keys);             // the keys: only they come back
+        const size_t o_desc = carve(sizeof(Desc) * m);
+        std::vector<typename H::Part> at;
+        for (size_t q = 0; q < m; ++q) at.push_back(h.carve(c, q, carve));
+        c.img.assign(carve.off, 0);
+        TRY(refine_multi_scratch(engines[c.first], carve.off, &c.dev));
+        Desc* hd = (Desc*)(c.img.data() + o_desc);
+        for (size_t q = 0; q < m; ++q) {
+            for (int t = 0; t < h.keys(c.members[q]); ++t) c.keys_of(c.img.data(), q)[t] = incumbent_key(h.incumbent(c.members[q], t));
+            h.fill(c, q, at, &hd[q]);
+        }
+        ProtoTable pt;
+        size_t lds = 0;
+        TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
+        RetainGrid gr;
+        const unsigned grid = multi_grid(c, groups, gr);
+        drain.arm();
+        HIPCHK(hipMemcpyAsync(c.dev, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
+        DISPATCH(engines[0], h.template launch<S>(grid, lds, st, pt, (const Desc*)(c.dev + o_desc), gr));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(c.img.data(), c.dev, sizeof(unsigned long long) * n_keys, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));                           // the call's one synchronise
+    drain.disarm();
+    for (MultiChunk& c : chunks)
+        for (size_t q = 0; q < c.members.size(); ++q) {
+            const int k = c.members[q];
+            const unsigned long long* keys = c.keys_of(c.img.data(), q);
+            for (int t = 0; t < h.keys(k); ++t)
+                if (keys[t] != incumbent_key(h.incumbent(k, t))) h.won(k, t, keys[t]);
+        }
+    return 0;
+}
+
+template <class H>
+static int multi_commit_run(lqrrt_engine** engines, int n, const int32_t* horizons, int32_t* const* ids_out, int32_t* counts_out,
+                            hipStream_t st, const H& h) {
+    typedef typename H::Desc Desc;
+    std::vector<int> room((size_t)n, 0), parent((size_t)n, -1);
+    std::vector<long long> winner((size_t)n, 0);
+    for (int k = 0; k < n; ++k) {
+        counts_out[k] = 0;
+        if (!h.winner(k)) continue;                             // (not part of the launch)
+        room[k] = h.room(k);
+        parent[k] = h.parent(k);
+        winner[k] = 1;
+    }
+    std::vector<MultiChunk> chunks = multi_chunks(winner);
+    StreamDrain drain(st);
+    for (MultiChunk& c : chunks) {
+        const size_t m = c.members.size();
+        Carve carve;
+        multi_commit_head(c, room, carve);
+        const size_t o_desc = carve(sizeof(Desc) * m);
+        std::vector<typename H::Part> at;
+        for (size_t q = 0; q < m; ++q) at.push_back(h.carve(c, q, carve));
+        c.img.assign(carve.off, 0);
+        TRY(refine_multi_scratch(engines[c.first], carve.off, &c.dev));
+        Desc* hd = (Desc*)(c.img.data() + o_desc);
+        for (size_t q = 0; q < m; ++q) {
+            hd[q].out = c.out_of(c.dev, q);
+            hd[q].lens = c.lens_of(c.dev, q);
+            hd[q].base = engines[c.members[q]]->N;
+            h.fill(c, q, at, &hd[q]);
+        }
+        ProtoTable pt;
+        size_t lds = 0;
+        TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
+        drain.arm();
+        HIPCHK(hipMemcpyAsync(c.dev, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
+        DISPATCH(engines[0], h.template launch<S>((unsigned)m, lds, st, pt, (const Desc*)(c.dev + o_desc)));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(c.img.data(), c.dev, c.back, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));                           // the call's one synchronise
+    drain.disarm();
+    multi_commit_adopt(engines, chunks, parent, ids_out, counts_out);
+    return 0;
+}
+
 // every argument of every engine, before anything is written or launched; bufs[k]: engine k's plan and cost prefix
 static int refine_multi_check(lqrrt_engine** engines, int n, const int32_t* const* plans, const int32_t* plan_lens, const int32_t* tries,
                               const int32_t* horizons, std::vector<std::vector<int>>& bufs) {
@@ -350,67 +444,59 @@ static int refine_multi_check(lqrrt_engine** engines, int n, const int32_t* cons
     });
 }
 
-// behind the head of a chunk's image: a RefineDesc per member (a filled; what a search or a commit adds is left to the caller) and
-// the members' plans with their cost prefixes; allocates the image on both sides
-static int refine_multi_stage(lqrrt_engine** engines, const std::vector<std::vector<int>>& bufs, const int32_t* plan_lens, const int32_t* tries,
-                              const int32_t* horizons, MultiChunk& c, Carve& carve, char** d_img, size_t* o_desc) {
-    const int m = (int)c.members.size();
-    *o_desc = carve(sizeof(RefineDesc) * m);
-    std::vector<size_t> o_plan((size_t)m);
-    for (int q = 0; q < m; ++q) o_plan[q] = carve(sizeof(int) * bufs[c.members[q]].size());
-    c.img.assign(carve.off, 0);
-    TRY(refine_multi_scratch(engines[c.first], carve.off, d_img));
-    RefineDesc* hd = (RefineDesc*)(c.img.data() + *o_desc);
-    for (int q = 0; q < m; ++q) {
+// The refinement's hooks.  What its search and its commit share: behind the descriptors the members' plans with their cost
+// prefixes (bufs[k]), and the argument block of a RefineDesc.
+struct RefineMulti {
+    typedef RefineDesc Desc;
+    typedef size_t Part;                                        // where the member's plan lies
+    lqrrt_engine** engines;
+    const std::vector<std::vector<int>>& bufs;
+    const int32_t* plan_lens; const int32_t* tries; const int32_t* horizons;
+    size_t carve(const MultiChunk& c, size_t q, Carve& carve) const { return carve(sizeof(int) * bufs[c.members[q]].size()); }
+    void fill(MultiChunk& c, size_t q, const std::vector<size_t>& at, RefineDesc* d) const {
         const int k = c.members[q];
-        memcpy(c.img.data() + o_plan[q], bufs[k].data(), sizeof(int) * bufs[k].size());
-        refine_fill_args(engines[k], (const int*)(*d_img + o_plan[q]), plan_lens[k], tries[k], horizons[k], &hd[q].a);
-        hd[q].i = hd[q].j = -1;
+        memcpy(c.img.data() + at[q], bufs[k].data(), sizeof(int) * bufs[k].size());
+        refine_fill_args(engines[k], (const int*)(c.dev + at[q]), plan_lens[k], tries[k], horizons[k], &d->a);
     }
-    return 0;
-}
+};
 
-static int refine_search_multi_run(lqrrt_engine** engines, int n, const std::vector<std::vector<int>>& bufs, const int32_t* plan_lens,
-                                   const int32_t* tries, const int32_t* horizons, const int64_t* incumbents, int64_t* cost, int32_t* i_out,
-                                   int32_t* j_out, hipStream_t st) {
-    std::vector<long long> cands((size_t)n);
-    for (int k = 0; k < n; ++k) cands[k] = refine_candidates(plan_lens[k]);
-    std::vector<MultiChunk> chunks = multi_chunks(cands);
-    StreamDrain drain(st);
-    for (MultiChunk& c : chunks) {
-        const int m = (int)c.members.size();
-        Carve carve;
-        carve(sizeof(unsigned long long) * m);                  // the keys
-        char* d_img = nullptr;
-        size_t o_desc = 0;
-        TRY(refine_multi_stage(engines, bufs, plan_lens, tries, horizons, c, carve, &d_img, &o_desc));
-        RefineDesc* hd = (RefineDesc*)(c.img.data() + o_desc);
-        for (int q = 0; q < m; ++q) {
-            ((unsigned long long*)c.img.data())[q] = incumbent_key(incumbents[c.members[q]]);
-            hd[q].best = (unsigned long long*)d_img + q;
-        }
-        ProtoTable pt;
-        size_t lds = 0;
-        TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
-        RetainGrid gr;
-        const unsigned grid = multi_grid(c, cands, gr);
-        drain.arm();
-        HIPCHK(hipMemcpyAsync(d_img, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
-        DISPATCH(engines[0], hipLaunchKernelGGL((k_refine_search_multi<S>), dim3(grid), dim3(64), lds, st, pt,
-                                                (const RefineDesc*)(d_img + o_desc), gr));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c.img.data(), d_img, sizeof(unsigned long long) * m, hipMemcpyDeviceToHost, st));
+struct RefineSearchMulti : RefineMulti {
+    const int64_t* incumbents; int64_t* cost; int32_t* i_out; int32_t* j_out;
+    long long groups(int k) const { return refine_candidates(plan_lens[k]); }
+    int keys(int) const { return 1; }
+    int64_t incumbent(int k, int) const { return incumbents[k]; }
+    void fill(MultiChunk& c, size_t q, const std::vector<size_t>& at, RefineDesc* d) const {
+        RefineMulti::fill(c, q, at, d);
+        d->i = d->j = -1;
+        d->best = c.keys_of(c.dev, q);
     }
-    std::vector<unsigned long long> keys;
-    TRY(multi_search_keys(chunks, n, incumbents, st, drain, keys));
-    for (int k = 0; k < n; ++k) {
-        if (keys[k] == incumbent_key(incumbents[k])) continue;
-        cost[k] = (int64_t)(keys[k] >> 32);
-        i_out[k] = (int32_t)((keys[k] >> 16) & 0xffff);
-        j_out[k] = (int32_t)(keys[k] & 0xffff);
+    template <class S>
+    static void launch(unsigned grid, size_t lds, hipStream_t st, const ProtoTable& pt, const RefineDesc* ds, const RetainGrid& gr) {
+        hipLaunchKernelGGL((k_refine_search_multi<S>), dim3(grid), dim3(64), lds, st, pt, ds, gr);
     }
-    return 0;
-}
+    void won(int k, int, unsigned long long key) const {
+        cost[k] = (int64_t)(key >> 32);
+        i_out[k] = (int32_t)((key >> 16) & 0xffff);
+        j_out[k] = (int32_t)(key & 0xffff);
+    }
+};
+
+// The replay of one candidate (ci[k], cj[k]) per engine with a winner (ci[k] >= 0).  connect_goals' commit is this one too: per
+// winner the one-node plan [v] with the cost prefix [depth[v]] and the candidate (0, 0).
+struct RefineCommitMulti : RefineMulti {
+    const int32_t* ci; const int32_t* cj;
+    bool winner(int k) const { return ci[k] >= 0; }
+    int room(int k) const { return plan_lens[k] - 1 - cj[k] + tries[k]; }
+    int parent(int k) const { return bufs[k][(size_t)ci[k]]; }
+    void fill(MultiChunk& c, size_t q, const std::vector<size_t>& at, RefineDesc* d) const {
+        RefineMulti::fill(c, q, at, d);
+        d->i = ci[c.members[q]]; d->j = cj[c.members[q]];
+    }
+    template <class S>
+    static void launch(unsigned m, size_t lds, hipStream_t st, const ProtoTable& pt, const RefineDesc* ds) {
+        hipLaunchKernelGGL((k_refine_commit_multi<S>), dim3(m), dim3(64), lds, st, pt, ds, (int)m);
+    }
+};
 
 extern "C" int lqrrt_refine_search_multi(lqrrt_engine** engines, int n, const int32_t* const* plans, const int32_t* plan_lens,
                                          const int32_t* goal_tries, const int32_t* horizon_iters, const int64_t* incumbents,
@@ -424,53 +510,8 @@ extern "C" int lqrrt_refine_search_multi(lqrrt_engine** engines, int n, const in
     }
     TRY(use_device(engines[0]));
     for (int k = 0; k < n; ++k) { cost_out[k] = incumbents[k]; i_out[k] = -1; j_out[k] = -1; }
-    return refine_search_multi_run(engines, n, bufs, plan_lens, goal_tries, horizon_iters, incumbents, cost_out, i_out, j_out, (hipStream_t)stream);
-}
-
-// The replay of one candidate (ci[k], cj[k]) per engine with a winner (ci[k] >= 0), one workgroup each.  connect_goals' commit is
-// this one too: per winner the one-node plan [v] with the cost prefix [depth[v]] and the candidate (0, 0).
-static int refine_commit_multi_run(lqrrt_engine** engines, int n, const std::vector<std::vector<int>>& bufs, const int32_t* plan_lens,
-                                   const int32_t* tries, const int32_t* horizons, const int32_t* ci, const int32_t* cj, int32_t* const* ids_out,
-                                   int32_t* counts_out, hipStream_t st) {
-    std::vector<int> room((size_t)n, 0), parent((size_t)n, -1);
-    std::vector<long long> winner((size_t)n, 0);
-    for (int k = 0; k < n; ++k) {
-        counts_out[k] = 0;
-        if (ci[k] < 0) continue;                                // (no winner: not part of the launch)
-        room[k] = plan_lens[k] - 1 - cj[k] + tries[k];
-        parent[k] = bufs[k][(size_t)ci[k]];
-        winner[k] = 1;
-    }
-    std::vector<MultiChunk> chunks = multi_chunks(winner);
-    StreamDrain drain(st);
-    for (MultiChunk& c : chunks) {
-        const int m = (int)c.members.size();
-        Carve carve;
-        multi_commit_head(c, room, carve);
-        char* d_img = nullptr;
-        size_t o_desc = 0;
-        TRY(refine_multi_stage(engines, bufs, plan_lens, tries, horizons, c, carve, &d_img, &o_desc));
-        RefineDesc* hd = (RefineDesc*)(c.img.data() + o_desc);
-        for (int q = 0; q < m; ++q) {
-            const int k = c.members[q];
-            hd[q].out = c.out_of(d_img, q);
-            hd[q].lens = c.lens_of(d_img, q);
-            hd[q].i = ci[k]; hd[q].j = cj[k]; hd[q].base = engines[k]->N;
-        }
-        ProtoTable pt;
-        size_t lds = 0;
-        TRY(refine_multi_protos(engines, c, horizons, st, pt, lds));
-        drain.arm();
-        HIPCHK(hipMemcpyAsync(d_img, c.img.data(), c.img.size(), hipMemcpyHostToDevice, st));
-        DISPATCH(engines[0], hipLaunchKernelGGL((k_refine_commit_multi<S>), dim3((unsigned)m), dim3(64), lds, st, pt,
-                                                (const RefineDesc*)(d_img + o_desc), m));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c.img.data(), d_img, c.back, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    drain.disarm();
-    multi_commit_adopt(engines, chunks, parent, ids_out, counts_out);
-    return 0;
+    return multi_search_run(engines, n, horizon_iters, (hipStream_t)stream,
+                            RefineSearchMulti{{engines, bufs, plan_lens, goal_tries, horizon_iters}, incumbents, cost_out, i_out, j_out});
 }
 
 extern "C" int lqrrt_refine_commit_multi(lqrrt_engine** engines, int n, const int32_t* const* plans, const int32_t* plan_lens,
@@ -488,5 +529,6 @@ extern "C" int lqrrt_refine_commit_multi(lqrrt_engine** engines, int n, const in
             return fail(LQRRT_E_ARG, "ids_out of engine %d must hold %d ids", k, P - 1 - j[k] + goal_tries[k]);
     }
     TRY(use_device(engines[0]));
-    return refine_commit_multi_run(engines, n, bufs, plan_lens, goal_tries, horizon_iters, i, j, ids_out, counts_out, (hipStream_t)stream);
+    return multi_commit_run(engines, n, horizon_iters, ids_out, counts_out, (hipStream_t)stream,
+                            RefineCommitMulti{{engines, bufs, plan_lens, goal_tries, horizon_iters}, i, j});
 }

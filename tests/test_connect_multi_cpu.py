@@ -139,6 +139,16 @@ def test_fleet_connection_stays_plain_launches():
     assert "static int connect_depths(" in host and host.count("TRY(connect_depths(") == 2
     for f in ("engine_reach.hpp", "engine_connect_via.hpp", "engine_connect_via_multi.hpp"):
         assert texts[f].count("TRY(connect_depths(") == 1, f
-    # the batched commit has no kernel and no runner of its own: it is the refinement's
-    assert "refine_multi_scratch(" in host and "refine_commit_multi_run(" in host and "k_refine_commit_multi" not in host
+    # the batched commit has no kernel and no hooks of its own: it is the shared commit runner with the refinement's hooks
+    refine = texts["engine_refine.hpp"]
+    search = refine[refine.index("static int multi_search_run("):refine.index("static int multi_commit_run(")]
+    commit = refine[refine.index("static int multi_commit_run("):refine.index("static int refine_multi_check(")]
+    assert "refine_multi_scratch(" in search and "refine_multi_scratch(" in commit
+    assert "multi_search_run(" in host and "multi_commit_run(" in host and "RefineCommitMulti{" in host and "k_refine_commit_multi" not in host
     assert host.count("hipLaunchKernelGGL(") == 3                   # the solo search, the shared solo commit, the multi search
+    # the chunk loop of the fleet calls is written out in the two runners and in the clearance run, nowhere else
+    clear = texts["engine_clear_multi.hpp"]
+    clear_run = clear[clear.index("static int clear_multi_run("):clear.index("static int clear_multi_call(")]
+    assert search.count("multi_chunks(") == 1 and commit.count("multi_chunks(") == 1 and clear_run.count("multi_chunks(") == 1
+    assert sum(t.count("multi_chunks(") for t in texts.values()) == 4          # its definition and the three calls
+    assert sorted(set(re.findall(r"static int (\w*_multi_run)\(", "".join(texts.values())))) == ["clear_multi_run"]

@@ -182,15 +182,29 @@ def test_fleet_via_stays_plain_launches_that_wrap_the_solo_bodies():
     engine = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine.hip")).read()
     assert engine.index('#include "engine_connect_via.hpp"') < engine.index('#include "engine_connect_via_multi.hpp"')
     host = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine_connect_via_multi.hpp")).read()
-    # the shared checks, depth functions, scratch, proto sync, grid and adopt rather than copies: connect_via_winner_check stands for
-    # range_ok and connect_depth_of, refine_multi_protos for multi_sync_proto, multi_grid for retain_grid, multi_commit_adopt for
-    # refine_adopt; a failed call drains the stream (StreamDrain, armed before every upload)
+    # the shared checks, depth functions and the two runners rather than copies: connect_via_winner_check stands for range_ok and
+    # connect_depth_of; the runners (engine_refine.hpp) for the chunks, the scratch, refine_multi_protos for multi_sync_proto,
+    # multi_grid for retain_grid, the keys' read-back and multi_commit_adopt for refine_adopt; a failed call drains the stream
+    # (StreamDrain: one in each runner, armed before the runner's only upload)
     for name in ("connect_multi_check(", "connect_via_check(", "connect_depths(", "connect_via_winner_check(", "connect_via_candidates_check(",
-                 "connect_via_deepest_check(", "incumbent_check(", "multi_id_list(", "multi_chunks(", "multi_commit_head(",
-                 "refine_multi_scratch(", "refine_multi_protos(", "multi_grid(", "multi_search_keys(", "multi_commit_adopt(",
-                 "StreamDrain drain(st)", "connect_via_fill_args(", "connect_via_decode("):
+                 "connect_via_deepest_check(", "incumbent_check(", "multi_id_list(", "multi_search_run(", "multi_commit_run(",
+                 "connect_via_fill_args(", "connect_via_decode("):
         assert name in host, name
-    assert host.count("StreamDrain drain(st)") == 2 and host.count("drain.arm();") == 2     # the search and the commit
+    refine = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine_refine.hpp")).read()
+    search = refine[refine.index("static int multi_search_run("):refine.index("static int multi_commit_run(")]
+    commit = refine[refine.index("static int multi_commit_run("):refine.index("static int refine_multi_check(")]
+    for name in ("multi_chunks(", "refine_multi_scratch(", "refine_multi_protos(", "multi_grid(", "keys_of("):
+        assert name in search, name
+    for name in ("multi_chunks(", "multi_commit_head(", "refine_multi_scratch(", "refine_multi_protos(", "multi_commit_adopt("):
+        assert name in commit, name
+    for f in ("engine_connect_via_multi.hpp", "engine_reach_multi.hpp", "engine_connect.hpp"):
+        text = open(os.path.join(ROOT, "lqrrt_amd", "csrc", f)).read()
+        multi = text[text.index("static int connect_multi_check("):] if f == "engine_connect.hpp" else text   # (its solo calls guard their own images)
+        assert "StreamDrain drain(st)" not in multi and "drain.arm();" not in multi, f
+    for run in (search, commit):                                    # the search and the commit
+        assert run.count("StreamDrain drain(st)") == 1 and run.count("drain.arm();") == 1
+        assert run.count("hipMemcpyHostToDevice") == 1
+        assert run.index("StreamDrain drain(st)") < run.index("drain.arm();") < run.index("hipMemcpyAsync(")
     assert "dalloc(" not in host and "hipMalloc" not in host       # no buffer of its own
     for copied in ("range_ok(", "connect_depth_of(", "multi_sync_proto(", "retain_grid(", "refine_adopt(", "0x7fffffff", "0xffffffff", "g_err"):
         assert copied not in host, copied

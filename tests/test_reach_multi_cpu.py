@@ -191,11 +191,21 @@ def test_reach_multi_stays_plain_launches():
     assert "- (unsigned)gr.block0[e]" in src                        # the body's block index is relative to the engine's first workgroup
     host = open(os.path.join(csrc, "engine_reach_multi.hpp")).read()
     assert host.count("hipLaunchKernelGGL(") == 2 and "k_reach_search_multi<S>" in host and "k_reach_commit_multi<S>" in host
-    for name in ("refine_multi_scratch(", "connect_depths(", "multi_commit_adopt(", "reach_target_fill(", "reach_target_check(",
-                 "multi_engines_check(", "multi_id_list(", "candidates_check(", "multi_chunks(", "multi_commit_head(", "multi_grid(",
-                 "refine_multi_protos(", "connect_winner_check("):
+    for name in ("connect_depths(", "reach_target_fill(", "reach_target_check(", "multi_engines_check(", "multi_id_list(", "candidates_check(",
+                 "connect_winner_check(", "multi_search_run(", "multi_commit_run("):
         assert name in host, name
-    assert "hipMalloc" not in host and "dalloc(" not in host and host.count("hipStreamSynchronize(") == 2   # one per call
+    # ... the two runners of engine_refine.hpp, which hold the chunks, the scratch, the grid and the call's one synchronise
+    refine = open(os.path.join(csrc, "engine_refine.hpp")).read()
+    search = refine[refine.index("static int multi_search_run("):refine.index("static int multi_commit_run(")]
+    commit = refine[refine.index("static int multi_commit_run("):refine.index("static int refine_multi_check(")]
+    for name in ("multi_chunks(", "refine_multi_scratch(", "multi_grid(", "refine_multi_protos("):
+        assert name in search, name
+    for name in ("multi_chunks(", "refine_multi_scratch(", "multi_commit_head(", "refine_multi_protos(", "multi_commit_adopt("):
+        assert name in commit, name
+    assert "hipMalloc" not in host and "dalloc(" not in host and "hipStreamSynchronize(" not in host
+    assert search.count("hipStreamSynchronize(") == 1 and commit.count("hipStreamSynchronize(") == 1          # one per call
+    for run in (search, commit):
+        assert run.index("HIPCHK(hipStreamSynchronize(st));") < run.index("drain.disarm();")
     kernels = open(os.path.join(csrc, "kernels.hpp")).read()
     assert kernels.index('#include "reach.hpp"') < kernels.index('#include "reach_multi.hpp"')
     engine = open(os.path.join(csrc, "engine.hip")).read()
