@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import retain_reference as rr
+from retain_compare import check_retained
 
 pytestmark = pytest.mark.gpu
 
@@ -61,24 +62,7 @@ def _retain_and_compare(eng, s, root, revalidate, oracle=None):
     ref = rr.retain(*arr, root, o.feasible if revalidate else None, lo, hi)
     stats, old_to_new = eng.tree_retain(root, revalidate=revalidate)
     print("retain root %d revalidate %s: %s" % (root, revalidate, stats))
-    assert stats == ref["stats"]
-    np.testing.assert_array_equal(old_to_new, ref["old_to_new"])
-    M = ref["stats"]["kept"]
-    assert eng.size == M
-    np.testing.assert_array_equal(eng.states(), ref["state"])
-    np.testing.assert_array_equal(eng.gains(), ref["K"])
-    np.testing.assert_array_equal(eng.parents(), ref["pID"])
-    xe, ue, ln = eng.edges()
-    np.testing.assert_array_equal(ln, ref["elen"])
-    live = np.arange(xe.shape[1])[None, :] < ln[:, None]
-    np.testing.assert_array_equal(xe[live], ref["xedge"][live])
-    np.testing.assert_array_equal(ue[live], ref["uedge"][live])
-    np.testing.assert_array_equal(eng.ignored(), ref["ignored"])
-    assert eng.plan_best() == (ref["stats"]["best_end"], ref["stats"]["best_steps"], ref["stats"]["goal_hits"])
-    best = ref["stats"]["best_end"]
-    assert eng.climb(max(best, 0))[0] == 0                                       # the host mirror of the parents follows
-    x, u = eng.edge(0)
-    assert len(x) == 1 and np.array_equal(x[0], ref["state"][0]) and not u.any()
+    check_retained(eng, ref, stats, old_to_new)
     return ref
 
 
