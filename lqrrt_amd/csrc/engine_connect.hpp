@@ -10,9 +10,10 @@
 // below v.
 //
 // The depth table is computed HERE, from the host mirrors of the parents and edge lengths in one ascending pass, and uploaded with
-// the call (4 B per node: 0.4 MB and well under a millisecond at 10^5 nodes).  It lives with the candidate ids and the results in
-// one scratch (d_con) that grows on demand and is, like d_ref, not part of lqrrt_engine_footprint.  The calls for several trees
-// (lqrrt_connect_*_multi, connect_goals) follow the one-tree calls below.
+// the call (4 B per node: 0.4 MB and well under a millisecond at 10^5 nodes).  The image of a search (engine_refine.hpp: the solo
+// runners and their scratch): the head (the key), the depth table [N], the candidate ids [count]; that of a commit: the head
+// (out[3]), the one-node plan [node] and its cost prefix [depth].  The calls for several trees (lqrrt_connect_*_multi,
+// connect_goals) follow the one-tree calls below.
 // --------------------------------------------------------------------------------------------
 
 static int connect_check(lqrrt_engine* e, int tries, int horizon) {
@@ -20,17 +21,6 @@ static int connect_check(lqrrt_engine* e, int tries, int horizon) {
     if (!e->has_res || !e->has_goal) return fail(LQRRT_E_STATE, "set_resolution with a goal first");
     if (horizon < 1 || horizon > e->H) return fail(LQRRT_E_ARG, "horizon of %d steps (the edge pools hold %d)", horizon, e->H);
     if (e->N < 1) return fail(LQRRT_E_STATE, "the tree is empty");
-    return 0;
-}
-
-// room for `ints` ints behind the head of 8
-static int connect_scratch(lqrrt_engine* e, size_t ints) {
-    if (e->d_con && ints <= e->con_cap) return 0;
-    if (e->d_con) (void)hipFree(e->d_con);
-    e->d_con = nullptr; e->con_cap = 0;
-    const size_t want = (ints + 1023) / 1024 * 1024;
-    TRY(dalloc_transient(&e->d_con, want + 8));                 // (allocated on first use: not part of the footprint)
-    e->con_cap = want;
     return 0;
 }
 
@@ -87,6 +77,48 @@ static void connect_fill_args(const lqrrt_engine* e, const int* depth_dev, const
     goal_fill(e, e->goal, a->goal);
 }
 
+// a winner's key: (cost, node)
+static void connect_decode(unsigned long long key, int64_t* cost, int32_t* node) {
+    *cost = (int64_t)(key >> 32);
+    *node = (int32_t)(key & 0xffffffffull);
+}
+
+// What a search over the nodes of one tree (connect, via, reach) keeps of its candidates -- the depth table, the id list (null:
+// every node), the candidate count -- and the one staging of the table and the optional list into the call's image.
+struct SoloCands {
+    std::vector<int> depth;
+    const int32_t* ids; int count;
+    size_t bytes() const { return sizeof(int) * (depth.size() + (ids ? (size_t)count : 0)); }
+    // the table and the list to `host`, and depth / nodes / count of the argument block
+    template <class Args>
+    void stage(char* host, const char* dev, Args* a) const {
+        const size_t o_ids = sizeof(int) * depth.size();
+        memcpy(host, depth.data(), o_ids);
+        if (ids) memcpy(host + o_ids, ids, sizeof(int) * (size_t)count);
+        a->depth = (const int*)dev;
+        a->nodes = ids ? (const int*)(dev + o_ids) : nullptr;
+        a->count = count;
+    }
+};
+
+// the search's hooks (engine_refine.hpp: solo_search_run), over its candidates
+struct ConnectSearchSolo : SoloCands {
+    typedef ConnectArgs Args;
+    int tries, horizon; int64_t best; int64_t* cost; int32_t* node_out;
+    long long groups() const { return count; }
+    int keys() const { return 1; }
+    int64_t incumbent(int) const { return best; }               // (incumbent, node 0)
+    void fill(const lqrrt_engine* e, char* host, const char* dev, ConnectArgs* a) const {
+        connect_fill_args(e, nullptr, nullptr, 0, tries, horizon, a);
+        stage(host, dev, a);
+    }
+    template <class S>
+    static void launch(const lqrrt_engine* e, unsigned grid, size_t lds, hipStream_t st, const ConnectArgs& a, unsigned long long* key) {
+        hipLaunchKernelGGL((k_connect_search<S>), dim3(grid), dim3(64), lds, st, e->P, e->geo, e->res, e->tv, a, key);
+    }
+    void won(int, unsigned long long key) const { connect_decode(key, cost, node_out); }
+};
+
 extern "C" int lqrrt_connect_search(lqrrt_engine* e, const int32_t* nodes_host, int count, int goal_tries, int horizon_iters,
                                     int64_t incumbent, int64_t* cost, int32_t* node_out, void* stream) {
     NOT_GENERIC(e);
@@ -94,37 +126,10 @@ extern "C" int lqrrt_connect_search(lqrrt_engine* e, const int32_t* nodes_host, 
     TRY(incumbent_check(incumbent, -1));
     TRY(connect_check(e, goal_tries, horizon_iters));
     TRY(connect_candidates_check(e, nodes_host, &count, -1));
-    const int N = e->N;
-    // the image of the call: head (the key), depth [N], candidate ids [count]
-    std::vector<int> img((size_t)8 + N + (nodes_host ? count : 0), 0);
-    int* depth = img.data() + 8;
-    TRY(connect_depths(e, goal_tries, horizon_iters, depth));
-    if (nodes_host && count) memcpy(depth + N, nodes_host, sizeof(int) * (size_t)count);
-    const unsigned long long init = incumbent_key(incumbent);   // (incumbent, node 0)
-    memcpy(img.data(), &init, sizeof init);
+    ConnectSearchSolo h{{std::vector<int>((size_t)e->N), nodes_host, count}, goal_tries, horizon_iters, incumbent, cost, node_out};
+    TRY(connect_depths(e, goal_tries, horizon_iters, h.depth.data()));
     *cost = incumbent; *node_out = -1;
-    if (count == 0) return 0;
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(connect_scratch(e, img.size() - 8));
-    unsigned long long key = init;
-    StreamDrain drain(st);                                      // (img is the source of a copy, key the target of one)
-    drain.arm();
-    HIPCHK(hipMemcpyAsync(e->d_con, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, st));
-    ConnectArgs a;
-    connect_fill_args(e, e->d_con + 8, nodes_host ? e->d_con + 8 + N : nullptr, count, goal_tries, horizon_iters, &a);
-    unsigned long long* d_key = (unsigned long long*)e->d_con;
-    DISPATCH(e, hipLaunchKernelGGL((k_connect_search<S>), dim3((unsigned)count), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P,
-                                   e->geo, e->res, e->tv, a, d_key));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&key, d_key, sizeof key, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    drain.disarm();
-    if (key != init) {
-        *cost = (int64_t)(key >> 32);
-        *node_out = (int32_t)(key & 0xffffffffull);
-    }
-    return 0;
+    return solo_search_run(e, horizon_iters, (hipStream_t)stream, h);
 }
 
 // A commit's winner `node` (a node of the tree) with a chain of up to `targets` edges below it: ids_out has room for their ids, and
@@ -138,31 +143,18 @@ static int connect_winner_check(const lqrrt_engine* e, int node, long long targe
     return 0;
 }
 
-// The replay of a search's winner, behind the caller's checks: k_refine_commit on the one-node "plan" [node] with the cost prefix
-// [depth], i = j = 0, steers goal_tries times at `goal` and appends the non-empty edges below `node`; the chain ends inside the
-// goal box of `res`.  lqrrt_connect_commit passes the engine's own goal and resolution block, lqrrt_reach_commit a target's
-// (`end`: what the messages call it).
+// The replay of a search's winner, behind the caller's checks: the refinement's commit (solo_commit_run with RefineCommitSolo:
+// k_refine_commit) on the one-node "plan" [node] with the cost prefix [depth], i = j = 0, steers goal_tries times at `goal` and
+// appends the non-empty edges below `node`; the chain ends inside the goal box of `res`.  lqrrt_connect_commit passes the engine's
+// own goal and resolution block, lqrrt_reach_commit a target's (`end`: what the messages call it).
 static int connect_commit_run(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, const double* goal, const Res& res,
                               const char* end, int32_t* ids_out, int cap_ids, void* stream) {
     long long depth = 0;
     TRY(connect_winner_check(e, node, goal_tries, horizon_iters, ids_out, cap_ids, -1, &depth));
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(connect_scratch(e, 2));
-    const int img[10] = {0, 0, 0, 0, 0, 0, 0, 0, node, (int)depth};
-    StreamDrain drain(st);                                      // (img is the source of a copy)
-    drain.arm();
-    HIPCHK(hipMemcpyAsync(e->d_con, img, sizeof img, hipMemcpyHostToDevice, st));
-    RefineArgs a;
-    refine_fill_args(e, e->d_con + 8, 1, goal_tries, horizon_iters, &a);
-    goal_fill(e, goal, a.goal);
-    const int base = e->N;
-    int* d_out = e->d_con + 2;
-    DISPATCH(e, hipLaunchKernelGGL((k_refine_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, res,
-                                   e->tv, a, 0, 0, base, e->fix, d_out));
-    HIPCHK(hipGetLastError());
-    return commit_finish(e, d_out, base, node, ids_out, st, drain, strf("the chain to the %s", end).c_str(),
-                         strf("the chain below node %d does not reach the %s: nothing appended", node, end).c_str());
+    const std::vector<int> buf = {node, (int)depth};
+    return solo_commit_run(e, horizon_iters, node, ids_out, (hipStream_t)stream,
+                           RefineCommitSolo{{buf, 1, goal_tries, horizon_iters, goal}, 0, 0, res}, strf("the chain to the %s", end).c_str(),
+                           strf("the chain below node %d does not reach the %s: nothing appended", node, end).c_str());
 }
 
 extern "C" int lqrrt_connect_commit(lqrrt_engine* e, int node, int goal_tries, int horizon_iters, int32_t* ids_out, int cap_ids,
@@ -240,10 +232,7 @@ struct ConnectSearchMulti {
     static void launch(unsigned grid, size_t lds, hipStream_t st, const ProtoTable& pt, const ConnectDesc* ds, const RetainGrid& gr) {
         hipLaunchKernelGGL((k_connect_search_multi<S>), dim3(grid), dim3(64), lds, st, pt, ds, gr);
     }
-    void won(int k, int, unsigned long long key) const {
-        cost[k] = (int64_t)(key >> 32);
-        node_out[k] = (int32_t)(key & 0xffffffffull);
-    }
+    void won(int k, int, unsigned long long key) const { connect_decode(key, &cost[k], &node_out[k]); }
 };
 
 extern "C" int lqrrt_connect_search_multi(lqrrt_engine** engines, int n, const int32_t* const* nodes, const int32_t* counts,

@@ -1,6 +1,6 @@
 // ABI: tree-wide goal chains through waypoints -- the search over (node, first waypoint) pairs and the commit of its winner
 // (Planner.connect_via; kernels in connect_via.hpp, the rule restated from the C oracle's primitives in
-// tests/connect_via_reference.py).  Fragment of engine.hip, behind engine_connect.hpp whose checks, depth table and scratch it uses.
+// tests/connect_via_reference.py).  Fragment of engine.hip, behind engine_connect.hpp whose checks, depth table and candidates it uses.
 //
 // The rule: engine_connect.hpp's tree and depth table; waypoints w_0 .. w_{Q-1}, Q >= 0, states of n doubles that need be neither
 // tree nodes nor feasible.  A candidate is a pair (v, j), 0 <= j <= Q, v every node or those of the caller's strictly ascending id
@@ -9,8 +9,8 @@
 // non-empty edge the chain ends valid if its end lies strictly inside the goal box; when the targets run out it is invalid.
 // Winner: the valid candidate of smallest (cost, v, j) with cost < incumbent.  With Q = 0 this is lqrrt_connect_search's rule.
 //
-// One image per call in d_con: the head of 8 ints (the key; a commit's out[3] behind it), the waypoints [Q][n] (8-byte aligned
-// behind the head), the depth table [N], the id list [count].  One copy up, one launch, one read-back.
+// One image per call (engine_refine.hpp: the solo runners and their scratch): the head (a search's key, a commit's out[3]), the
+// waypoints [Q][n] (8-byte aligned behind the head) and, in a search, the depth table [N] and the id list [count].
 //
 // The checks, the argument block and the key's decoding below serve the calls for several trees too (engine_connect_via_multi.hpp).
 // --------------------------------------------------------------------------------------------
@@ -70,6 +70,44 @@ static void connect_via_decode(unsigned long long key, const int32_t* ids, int Q
     *j = (int32_t)(cand - pos * ((long long)Q + 1));
 }
 
+// The solo hooks.  What the search and the commit share: behind the head the waypoints (`way`: way_bytes bytes), and the argument block.
+struct ConnectViaSolo {
+    typedef ConnectViaArgs Args;
+    const double* way; size_t way_bytes;
+    int Q, tries, horizon;
+    size_t bytes() const { return way_bytes; }
+    void fill(const lqrrt_engine* e, char* host, const char* dev, ConnectViaArgs* a) const {
+        if (way_bytes) memcpy(host, way, way_bytes);
+        connect_via_fill_args(e, (const double*)dev, Q, tries, horizon, a);
+    }
+};
+
+struct ConnectViaSearchSolo : ConnectViaSolo, SoloCands {
+    int64_t best; int64_t* cost; int32_t* node_out; int32_t* j_out;
+    size_t bytes() const { return way_bytes + SoloCands::bytes(); }
+    long long groups() const { return (long long)count * (Q + 1); }
+    int keys() const { return 1; }
+    int64_t incumbent(int) const { return best; }               // (incumbent, candidate 0)
+    void fill(const lqrrt_engine* e, char* host, const char* dev, ConnectViaArgs* a) const {
+        ConnectViaSolo::fill(e, host, dev, a);
+        stage(host + way_bytes, dev + way_bytes, a);
+    }
+    template <class S>
+    static void launch(const lqrrt_engine* e, unsigned grid, size_t lds, hipStream_t st, const ConnectViaArgs& a, unsigned long long* key) {
+        hipLaunchKernelGGL((k_connect_via_search<S>), dim3(grid), dim3(64), lds, st, e->P, e->geo, e->res, e->tv, a, key);
+    }
+    void won(int, unsigned long long key) const { connect_via_decode(key, ids, Q, cost, node_out, j_out); }
+};
+
+// the replay of candidate (node, j), `depth` steps from the root
+struct ConnectViaCommitSolo : ConnectViaSolo {
+    int node, j, depth;
+    template <class S>
+    void launch(const lqrrt_engine* e, size_t lds, hipStream_t st, const ConnectViaArgs& a, int base, int* out) const {
+        hipLaunchKernelGGL((k_connect_via_commit<S>), dim3(1), dim3(64), lds, st, e->P, e->geo, e->res, e->tv, a, node, j, depth, base, e->fix, out);
+    }
+};
+
 extern "C" int lqrrt_connect_via_search(lqrrt_engine* e, const int32_t* nodes_host, int count, const double* waypoints_host, int Q,
                                         int goal_tries, int horizon_iters, int64_t incumbent, int64_t* cost, int32_t* node_out,
                                         int32_t* j_out, void* stream) {
@@ -78,41 +116,12 @@ extern "C" int lqrrt_connect_via_search(lqrrt_engine* e, const int32_t* nodes_ho
     TRY(incumbent_check(incumbent, -1));
     TRY(connect_via_check(e, waypoints_host, Q, goal_tries, horizon_iters));
     TRY(connect_via_candidates_check(e, nodes_host, &count, Q, -1));
-    const int N = e->N;
-    // the image of the call: head (the key), waypoints [Q][n], depth [N], candidate ids [count]
-    const size_t way_ints = (size_t)2 * Q * e->n;
-    std::vector<int> img((size_t)8 + way_ints + N + (nodes_host ? count : 0), 0);
-    int* depth = img.data() + 8 + way_ints;
-    TRY(connect_depths(e, 0, horizon_iters, depth));
-    TRY(connect_via_deepest_check(depth, N, nodes_host, count, Q, goal_tries, horizon_iters, -1));
-    if (way_ints) memcpy(img.data() + 8, waypoints_host, sizeof(int) * way_ints);
-    if (nodes_host && count) memcpy(depth + N, nodes_host, sizeof(int) * (size_t)count);
-    const unsigned long long init = incumbent_key(incumbent);   // (incumbent, candidate 0)
-    memcpy(img.data(), &init, sizeof init);
+    ConnectViaSearchSolo h{{waypoints_host, sizeof(double) * Q * e->n, Q, goal_tries, horizon_iters},
+                           {std::vector<int>((size_t)e->N), nodes_host, count}, incumbent, cost, node_out, j_out};
+    TRY(connect_depths(e, 0, horizon_iters, h.depth.data()));
+    TRY(connect_via_deepest_check(h.depth.data(), e->N, nodes_host, count, Q, goal_tries, horizon_iters, -1));
     *cost = incumbent; *node_out = -1; *j_out = -1;
-    if (count == 0) return 0;
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(connect_scratch(e, img.size() - 8));
-    unsigned long long key = init;
-    StreamDrain drain(st);                                      // (img is the source of a copy, key the target of one)
-    drain.arm();
-    HIPCHK(hipMemcpyAsync(e->d_con, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, st));
-    ConnectViaArgs a;
-    connect_via_fill_args(e, (const double*)(e->d_con + 8), Q, goal_tries, horizon_iters, &a);
-    a.depth = e->d_con + 8 + way_ints;
-    a.nodes = nodes_host ? a.depth + N : nullptr;
-    a.count = count;
-    unsigned long long* d_key = (unsigned long long*)e->d_con;
-    const unsigned grid = (unsigned)((long long)count * (Q + 1));
-    DISPATCH(e, hipLaunchKernelGGL((k_connect_via_search<S>), dim3(grid), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo,
-                                   e->res, e->tv, a, d_key));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&key, d_key, sizeof key, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    drain.disarm();
-    if (key != init) connect_via_decode(key, nodes_host, Q, cost, node_out, j_out);
-    return 0;
+    return solo_search_run(e, horizon_iters, (hipStream_t)stream, h);
 }
 
 // a commit's winner (node, j): what connect_winner_check asks of its Q - j + tries targets; *room: their number
@@ -132,22 +141,8 @@ extern "C" int lqrrt_connect_via_commit(lqrrt_engine* e, int node, int j, const 
     long long depth = 0;
     int room = 0;
     TRY(connect_via_winner_check(e, node, j, Q, goal_tries, horizon_iters, ids_out, cap_ids, -1, &depth, &room));
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t way_ints = (size_t)2 * Q * e->n;
-    TRY(connect_scratch(e, way_ints));
-    std::vector<int> img((size_t)8 + way_ints, 0);
-    if (way_ints) memcpy(img.data() + 8, waypoints_host, sizeof(int) * way_ints);
-    StreamDrain drain(st);                                      // (img is the source of a copy)
-    drain.arm();
-    HIPCHK(hipMemcpyAsync(e->d_con, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, st));
-    ConnectViaArgs a;
-    connect_via_fill_args(e, (const double*)(e->d_con + 8), Q, goal_tries, horizon_iters, &a);
-    const int base = e->N;
-    int* d_out = e->d_con + 2;
-    DISPATCH(e, hipLaunchKernelGGL((k_connect_via_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo,
-                                   e->res, e->tv, a, node, j, (int)depth, base, e->fix, d_out));
-    HIPCHK(hipGetLastError());
-    return commit_finish(e, d_out, base, node, ids_out, st, drain, "the chain to the goal",
-                         strf("the chain of candidate (%d, %d) does not reach the goal: nothing appended", node, j).c_str());
+    return solo_commit_run(e, horizon_iters, node, ids_out, (hipStream_t)stream,
+                           ConnectViaCommitSolo{{waypoints_host, sizeof(double) * Q * e->n, Q, goal_tries, horizon_iters}, node, j, (int)depth},
+                           "the chain to the goal",
+                           strf("the chain of candidate (%d, %d) does not reach the goal: nothing appended", node, j).c_str());
 }

@@ -34,7 +34,7 @@ static void free_all(lqrrt_engine* e) {
                     e->d_pidx, e->d_par_want, e->d_list,
                     e->d_need, e->d_summary, e->d_pool, e->d_pool_trig, e->d_pool_S, e->d_QR, e->d_Sop, e->d_cand, e->d_flags,
                     e->d_head2, e->d_rank,
-                    e->d_blk, e->d_blk_cursor, e->d_ref, e->d_ref_key, e->d_refm, e->d_con};
+                    e->d_blk, e->d_blk_cursor, e->d_solo, e->d_refm};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (e->h_ign_pin) (void)hipHostFree(e->h_ign_pin);

@@ -1,12 +1,13 @@
 // ABI: one tree asked about many goals -- the search for T targets in one launch and the commit of one target's winner
 // (Planner.goal_costs / Planner.retarget; kernel in reach.hpp, the rule restated from the C oracle's primitives in
-// tests/reach_reference.py).  Fragment of engine.hip, behind engine_connect.hpp whose checks, depth table and scratch it uses.
+// tests/reach_reference.py).  Fragment of engine.hip, behind engine_connect.hpp whose checks, depth table and candidates it uses.
 //
 // The rule: engine_connect.hpp's, with a target's goal state g_t and box lo_t < x < hi_t in place of the engine's own, for every
 // target independently.  The engine's goal and box are read by neither call and written by neither.
 //
-// One image per search in d_con, the 8-byte parts first: the keys [T] (64 bit), the target table [T] (ReachTarget: goal, lo, hi),
-// the depth table [N], the id list [count].  One copy up, one launch, the T keys back in one copy.
+// One image per search (engine_refine.hpp: the solo runner and its scratch), the 8-byte parts first: the head (the keys [T], 64
+// bit), the target table [T] (ReachTarget: goal, lo, hi), the depth table [N], the id list [count].  The commit's image is the
+// connect commit's.
 // --------------------------------------------------------------------------------------------
 
 // a target as the caller gave it: finite goal, lo <= hi in the model's dimensions
@@ -28,6 +29,33 @@ static void reach_target_fill(const lqrrt_engine* e, const double* goal, const d
     }
 }
 
+// the incumbent of target t: the caller's, or none (every reaching chain wins)
+static long long reach_incumbent(const int64_t* incumbents, int t) { return incumbents ? (long long)incumbents[t] : 0x7fffffffLL; }
+
+// the search's hooks (engine_refine.hpp: solo_search_run): a key per target
+struct ReachSearchSolo : SoloCands {
+    typedef ReachArgs Args;
+    const double* goals; const double* lo; const double* hi;
+    int T, tries, horizon; const int64_t* incumbents; int64_t* cost; int32_t* node_out;
+    size_t bytes() const { return sizeof(ReachTarget) * (size_t)T + SoloCands::bytes(); }
+    long long groups() const { return (long long)T * count; }
+    int keys() const { return T; }
+    int64_t incumbent(int t) const { return reach_incumbent(incumbents, t); }   // (incumbent, node 0)
+    void fill(const lqrrt_engine* e, char* host, const char* dev, ReachArgs* a) const {
+        ReachTarget* tab = (ReachTarget*)host;
+        const size_t n = (size_t)e->n, o_cands = sizeof(ReachTarget) * (size_t)T;
+        for (int t = 0; t < T; ++t) reach_target_fill(e, goals + t * n, lo + t * n, hi + t * n, tab[t].goal, tab[t].lo, tab[t].hi);
+        a->targets = (const ReachTarget*)dev;
+        a->T = T; a->tries = tries; a->H = horizon;
+        stage(host + o_cands, dev + o_cands, a);
+    }
+    template <class S>
+    static void launch(const lqrrt_engine* e, unsigned grid, size_t lds, hipStream_t st, const ReachArgs& a, unsigned long long* keys) {
+        hipLaunchKernelGGL((k_reach_search<S>), dim3(grid), dim3(64), lds, st, e->P, e->geo, e->res, e->tv, a, keys);
+    }
+    void won(int t, unsigned long long key) const { connect_decode(key, &cost[t], &node_out[t]); }
+};
+
 extern "C" int lqrrt_reach_search(lqrrt_engine* e, const double* goals, const double* lo, const double* hi, int T,
                                   const int32_t* nodes_host, int count, int goal_tries, int horizon_iters, const int64_t* incumbents,
                                   int64_t* cost_out, int32_t* node_out, void* stream) {
@@ -38,54 +66,17 @@ extern "C" int lqrrt_reach_search(lqrrt_engine* e, const double* goals, const do
     TRY(candidates_check(e, nodes_host, &count, T, -1, [&](int c) {
         return fail(LQRRT_E_ARG, "%d targets of %d candidates: %lld workgroups exceed one launch", T, c, (long long)T * c);
     }));
-    const int N = e->N, n = e->n;
+    const size_t n = (size_t)e->n;
     for (int t = 0; t < T; ++t) {
-        const long long inc = incumbents ? (long long)incumbents[t] : 0x7fffffffLL;
+        const long long inc = reach_incumbent(incumbents, t);
         if (inc < 1 || inc > 0x7fffffffLL) return fail(LQRRT_E_ARG, "incumbent cost %lld of target %d out of range", inc, t);
-        TRY(reach_target_check(e, goals + (size_t)t * n, lo + (size_t)t * n, hi + (size_t)t * n, t));
+        TRY(reach_target_check(e, goals + t * n, lo + t * n, hi + t * n, t));
     }
-    // the image of the call: keys [T], targets [T], depth [N], candidate ids [count]
-    const size_t o_tab = sizeof(unsigned long long) * (size_t)T, o_depth = o_tab + sizeof(ReachTarget) * (size_t)T;
-    const size_t o_ids = o_depth + sizeof(int) * (size_t)N;
-    std::vector<unsigned long long> img((o_ids + sizeof(int) * (size_t)(nodes_host ? count : 0) + 7) / 8, 0);
-    char* base = (char*)img.data();
-    TRY(connect_depths(e, goal_tries, horizon_iters, (int*)(base + o_depth)));
-    if (nodes_host && count) memcpy(base + o_ids, nodes_host, sizeof(int) * (size_t)count);
-    ReachTarget* tab = (ReachTarget*)(base + o_tab);
-    for (int t = 0; t < T; ++t) {
-        cost_out[t] = incumbents ? incumbents[t] : 0x7fffffffLL;
-        node_out[t] = -1;
-        img[(size_t)t] = incumbent_key(cost_out[t]);             // (incumbent, node 0)
-        reach_target_fill(e, goals + (size_t)t * n, lo + (size_t)t * n, hi + (size_t)t * n, tab[t].goal, tab[t].lo, tab[t].hi);
-    }
-    if (count == 0) return 0;
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(connect_scratch(e, img.size() * 2));                    // (the scratch counts ints behind its head of 8; the image starts at the head)
-    std::vector<unsigned long long> keys((size_t)T);
-    StreamDrain drain(st);                                      // (img is the source of a copy, keys the target of one)
-    char* d_img = (char*)e->d_con;
-    drain.arm();
-    HIPCHK(hipMemcpyAsync(d_img, base, sizeof(unsigned long long) * img.size(), hipMemcpyHostToDevice, st));
-    ReachArgs a;
-    a.targets = (const ReachTarget*)(d_img + o_tab);
-    a.depth = (const int*)(d_img + o_depth);
-    a.nodes = nodes_host ? (const int*)(d_img + o_ids) : nullptr;
-    a.T = T; a.count = count; a.tries = goal_tries; a.H = horizon_iters;
-    unsigned long long* d_keys = (unsigned long long*)d_img;
-    const unsigned grid = (unsigned)((long long)T * count);
-    DISPATCH(e, hipLaunchKernelGGL((k_reach_search<S>), dim3(grid), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, e->res,
-                                   e->tv, a, d_keys));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(keys.data(), d_keys, sizeof(unsigned long long) * (size_t)T, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    drain.disarm();
-    for (int t = 0; t < T; ++t) {
-        if (keys[(size_t)t] == img[(size_t)t]) continue;
-        cost_out[t] = (int64_t)(keys[(size_t)t] >> 32);
-        node_out[t] = (int32_t)(keys[(size_t)t] & 0xffffffffull);
-    }
-    return 0;
+    ReachSearchSolo h{{std::vector<int>((size_t)e->N), nodes_host, count}, goals, lo, hi, T, goal_tries, horizon_iters, incumbents,
+                      cost_out, node_out};
+    TRY(connect_depths(e, goal_tries, horizon_iters, h.depth.data()));
+    for (int t = 0; t < T; ++t) { cost_out[t] = reach_incumbent(incumbents, t); node_out[t] = -1; }
+    return solo_search_run(e, horizon_iters, (hipStream_t)stream, h);
 }
 
 // lqrrt_connect_commit's replay (connect_commit_run) with the target as the chain's goal and a copy of the resolution block whose

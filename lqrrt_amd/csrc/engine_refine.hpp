@@ -4,10 +4,11 @@
 // The refinement is the first of a family of calls -- goal connection (engine_connect.hpp), one tree asked about many goals
 // (engine_reach.hpp), goal chains through waypoints (engine_connect_via.hpp, engine_connect_via_multi.hpp) -- that search candidates
 // in one launch and replay the winner in another.  What their host sides share is stated once, here where its first user is: the
-// rules of an argument (incumbent_check, goal_fill), the end of a one-engine commit (commit_finish), the guard of a call's host
-// images (StreamDrain), and for the calls that take several engines the engine-list check and the two runners that string a call's
-// chunks together (multi_search_run, multi_commit_run, with MultiChunk and the multi_* functions).  The kernel launched, its
-// descriptor, the tables behind it and the decoding of a key are each caller's own: its hooks.
+// rules of an argument (incumbent_check, goal_fill), the guard of a call's host images (StreamDrain), the one-engine calls' scratch
+// and their two runners (solo_scratch, solo_search_run, solo_commit_run), and for the calls that take several engines the
+// engine-list check and the two runners that string a call's chunks together (multi_search_run, multi_commit_run, with MultiChunk
+// and the multi_* functions).  The kernel launched, its argument block or descriptor, the tables behind it and the decoding of a
+// key are each caller's own: its hooks.
 // --------------------------------------------------------------------------------------------
 
 // " (engine k)" behind a message of a call for several engines; nothing behind that of a one-engine call (k < 0)
@@ -94,57 +95,8 @@ static void refine_fill_args(const lqrrt_engine* e, const int* plan_dev, int P, 
     goal_fill(e, e->goal, a->goal);
 }
 
-// Checks a plan and uploads its ids and cost prefix; `buf` holds the host copy until the caller has synchronised the stream.
-static int refine_prepare(lqrrt_engine* e, const int32_t* plan, int P, int tries, int horizon, std::vector<int>& buf, RefineArgs* a,
-                          hipStream_t st, StreamDrain& drain) {
-    TRY(refine_check(e, plan, P, tries, horizon, buf));
-    if (P > e->ref_cap) {
-        if (e->d_ref) (void)hipFree(e->d_ref);
-        e->ref_cap = 0;
-        TRY(dalloc_transient(&e->d_ref, (size_t)2 * P));        // (a few kB, allocated on first use: not part of the footprint)
-        if (!e->d_ref_key) TRY(dalloc_transient(&e->d_ref_key, (size_t)4));
-        e->ref_cap = P;
-    }
-    drain.arm();
-    HIPCHK(hipMemcpyAsync(e->d_ref, buf.data(), sizeof(int) * buf.size(), hipMemcpyHostToDevice, st));
-    refine_fill_args(e, e->d_ref, P, tries, horizon, a);
-    return 0;
-}
-
 static size_t refine_lds_bytes(const lqrrt_engine* e, int horizon) {
     return geo_lds_bytes(e) + ((size_t)horizon * (e->n + e->m) + e->n + 2 * e->nw + (size_t)e->m * e->n) * sizeof(double);
-}
-
-extern "C" int lqrrt_refine_search(lqrrt_engine* e, const int32_t* plan_host, int P, int goal_tries, int horizon_iters,
-                                   int64_t incumbent, int64_t* cost, int32_t* i_out, int32_t* j_out, void* stream) {
-    NOT_GENERIC(e);
-    if (!e || !cost || !i_out || !j_out) return fail(LQRRT_E_ARG, "null argument");
-    TRY(incumbent_check(incumbent, -1));
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<int> buf;
-    const unsigned long long init = incumbent_key(incumbent);
-    unsigned long long key = init;
-    StreamDrain drain(st);                                      // (buf and init are sources of copies, key the target of one)
-    RefineArgs a;
-    TRY(refine_prepare(e, plan_host, P, goal_tries, horizon_iters, buf, &a, st, drain));
-    *cost = incumbent; *i_out = -1; *j_out = -1;
-    if (P >= 2) {
-        TRY(refine_candidates_check(P));
-        HIPCHK(hipMemcpyAsync(e->d_ref_key, &init, sizeof init, hipMemcpyHostToDevice, st));
-        DISPATCH(e, hipLaunchKernelGGL((k_refine_search<S>), dim3((unsigned)refine_candidates(P)), dim3(64), refine_lds_bytes(e, horizon_iters),
-                                       st, e->P, e->geo, e->res, e->tv, a, e->d_ref_key));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&key, e->d_ref_key, sizeof key, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    drain.disarm();
-    if (key != init) {
-        *cost = (int64_t)(key >> 32);
-        *i_out = (int32_t)((key >> 16) & 0xffff);
-        *j_out = (int32_t)(key & 0xffff);
-    }
-    return 0;
 }
 
 // host mirrors of `count` appended nodes (a parent chain below `parent`), as lqrrt_tree_append keeps them: parents, edge lengths,
@@ -166,15 +118,87 @@ static void refine_adopt(lqrrt_engine* e, int parent, int count, const int* lens
     e->tot.tree_size = e->N;
 }
 
-// The end of a one-engine commit, behind the launch of a replay that appends below tree size `base` and writes d_out[3] (the node
-// count or -1: no room, -, 1: the chain reached its goal): the read-back, the call's one synchronise, the refusals, the new
-// edges' lengths and the host mirrors.  `holds`: what the tree cannot hold; `unreached`: the message of a chain that fell short.
-// Returns the number of nodes appended below `parent`, their ids in ids_out.
-static int commit_finish(lqrrt_engine* e, const int* d_out, int base, int parent, int32_t* ids_out, hipStream_t st, StreamDrain& drain,
-                         const char* holds, const char* unreached) {
+// --------------------------------------------------------------------------------------------
+// One engine per call (refine, connect, via and reach: a search and a commit each).  Every argument is checked by the call's export
+// before anything is written or launched.  A call has one image in device memory -- a head of SOLO_HEAD bytes for what comes back
+// (a search's best keys, from byte 0; a commit's out[3] at ints 2 to 4), behind it what the call's hooks lay out -- staged on the
+// host and uploaded in one copy; one launch; the keys or out[3] back in one copy; one synchronise.  The image lives in the engine's
+// d_solo, which grows on demand, is shared by all these calls (they are synchronous: nothing reads it after they return) and is
+// not part of lqrrt_engine_footprint.
+static const size_t SOLO_HEAD = 8 * sizeof(int);
+
+// An image's scratch (*mem of *cap bytes) with room for `bytes` bytes: allocated on first use and grown on demand in steps of 4 kB,
+// not part of the footprint.  The one-engine calls' and, further down, the chunks' of a call for several engines.
+static int scratch_grow(char** mem, size_t* cap, size_t bytes) {
+    if (*mem && bytes <= *cap) return 0;
+    if (*mem) (void)hipFree(*mem);
+    *mem = nullptr; *cap = 0;
+    const size_t want = (bytes + 4095) / 4096 * 4096;
+    TRY(dalloc_transient(mem, want));
+    *cap = want;
+    return 0;
+}
+
+// room in d_solo for an image of `bytes` bytes, head included
+static int solo_scratch(lqrrt_engine* e, size_t bytes) { return scratch_grow(&e->d_solo, &e->solo_cap, bytes); }
+
+// The two solo runners: what multi_search_run and multi_commit_run below are to a call for several engines.  They own use_device
+// and the order that makes a call safe -- the scratch is allocated before the guard, the guard stands behind the host image (whose
+// head a search's keys come back into) and a commit's out[3], it is armed before the only upload and disarmed only after the
+// synchronise that succeeded -- and a call states in a hooks object h only what is its own:
+//   h.Args                       the kernel's argument block
+//   h.bytes()                    the size of the image behind its head
+//   h.fill(e, host, dev, a)      stages the image behind the head at `host` and fills a; device addresses are those of `dev`
+//   h.launch<S>(...)             the one launch, which names the call's kernel
+// and, a search: h.groups(), its workgroups (0: no launch, and the device is not touched); h.keys(), its number of keys, and
+// h.incumbent(t), the cost behind key t, which starts as incumbent_key of it; h.won(t, key) for every key that the launch
+// replaced.  A commit replays on one workgroup a chain that appends below tree size `base` and writes out[3] (the node count or
+// -1: no room, -, 1: the chain reached its goal); the runner refuses what did not fit (`holds`: what the tree cannot hold) or fell
+// short (`unreached`: the message), reads the new edges' lengths and adopts the nodes below `parent`.  It returns their number,
+// their ids in ids_out.
+template <class H>
+static int solo_search_run(lqrrt_engine* e, int horizon, hipStream_t st, const H& h) {
+    const long long groups = h.groups();
+    if (groups == 0) return 0;                                  // (the outputs stay at "incumbent, -1")
+    TRY(use_device(e));
+    const size_t keys = (size_t)h.keys(), head = std::max(SOLO_HEAD, sizeof(unsigned long long) * keys);
+    TRY(solo_scratch(e, head + h.bytes()));
+    std::vector<char> img(head + h.bytes(), 0);
+    StreamDrain drain(st);                                      // (img is the source of a copy, its head the target of one)
+    unsigned long long* key = (unsigned long long*)img.data();
+    for (size_t t = 0; t < keys; ++t) key[t] = incumbent_key(h.incumbent((int)t));
+    typename H::Args a;
+    h.fill(e, img.data() + head, e->d_solo + head, &a);
+    drain.arm();
+    HIPCHK(hipMemcpyAsync(e->d_solo, img.data(), img.size(), hipMemcpyHostToDevice, st));
+    DISPATCH(e, h.template launch<S>(e, (unsigned)groups, refine_lds_bytes(e, horizon), st, a, (unsigned long long*)e->d_solo));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(key, e->d_solo, sizeof(unsigned long long) * keys, hipMemcpyDeviceToHost, st));     // the keys only
+    HIPCHK(hipStreamSynchronize(st));                           // the call's one synchronise
+    drain.disarm();
+    for (size_t t = 0; t < keys; ++t)
+        if (key[t] != incumbent_key(h.incumbent((int)t))) h.won((int)t, key[t]);
+    return 0;
+}
+
+template <class H>
+static int solo_commit_run(lqrrt_engine* e, int horizon, int parent, int32_t* ids_out, hipStream_t st, const H& h, const char* holds,
+                           const char* unreached) {
+    TRY(use_device(e));
+    TRY(solo_scratch(e, SOLO_HEAD + h.bytes()));
+    std::vector<char> img(SOLO_HEAD + h.bytes(), 0);
     int out[3] = {0, 0, 0};
+    StreamDrain drain(st);                                      // (img is the source of a copy, out the target of one)
+    typename H::Args a;
+    h.fill(e, img.data() + SOLO_HEAD, e->d_solo + SOLO_HEAD, &a);
+    const int base = e->N;
+    int* d_out = (int*)e->d_solo + 2;
+    drain.arm();
+    HIPCHK(hipMemcpyAsync(e->d_solo, img.data(), img.size(), hipMemcpyHostToDevice, st));
+    DISPATCH(e, h.template launch<S>(e, refine_lds_bytes(e, horizon), st, a, base, d_out));
+    HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(st));                           // the call's one synchronise
     drain.disarm();
     if (out[0] < 0) return fail(LQRRT_E_CAPACITY, "tree capacity %d cannot hold %s", e->cap, holds);
     if (!out[2]) return fail(LQRRT_E_STATE, "%s", unreached);
@@ -185,25 +209,75 @@ static int commit_finish(lqrrt_engine* e, const int* d_out, int base, int parent
     return count;
 }
 
+// a winner's key: (cost, i, j)
+static void refine_decode(unsigned long long key, int64_t* cost, int32_t* i, int32_t* j) {
+    *cost = (int64_t)(key >> 32);
+    *i = (int32_t)((key >> 16) & 0xffff);
+    *j = (int32_t)(key & 0xffff);
+}
+
+// The refinement's solo hooks.  What its search and its commit share: behind the head the plan with its cost prefix (buf), and
+// the argument block of chains that steer at `goal`.
+struct RefineSolo {
+    typedef RefineArgs Args;
+    const std::vector<int>& buf;
+    int P, tries, horizon;
+    const double* goal;
+    size_t bytes() const { return sizeof(int) * buf.size(); }
+    void fill(const lqrrt_engine* e, char* host, const char* dev, RefineArgs* a) const {
+        memcpy(host, buf.data(), bytes());
+        refine_fill_args(e, (const int*)dev, P, tries, horizon, a);
+        goal_fill(e, goal, a->goal);
+    }
+};
+
+struct RefineSearchSolo : RefineSolo {
+    int64_t best; int64_t* cost; int32_t* i_out; int32_t* j_out;
+    long long groups() const { return refine_candidates(P); }
+    int keys() const { return 1; }
+    int64_t incumbent(int) const { return best; }
+    template <class S>
+    static void launch(const lqrrt_engine* e, unsigned grid, size_t lds, hipStream_t st, const RefineArgs& a, unsigned long long* key) {
+        hipLaunchKernelGGL((k_refine_search<S>), dim3(grid), dim3(64), lds, st, e->P, e->geo, e->res, e->tv, a, key);
+    }
+    void won(int, unsigned long long key) const { refine_decode(key, cost, i_out, j_out); }
+};
+
+// The replay of candidate (i, j), its chain ending inside the goal box of `res`: the engine's own for a refinement; connect's
+// and reach's commit is this one too (engine_connect.hpp: connect_commit_run).
+struct RefineCommitSolo : RefineSolo {
+    int i, j;
+    const Res& res;
+    template <class S>
+    void launch(const lqrrt_engine* e, size_t lds, hipStream_t st, const RefineArgs& a, int base, int* out) const {
+        hipLaunchKernelGGL((k_refine_commit<S>), dim3(1), dim3(64), lds, st, e->P, e->geo, res, e->tv, a, i, j, base, e->fix, out);
+    }
+};
+
+extern "C" int lqrrt_refine_search(lqrrt_engine* e, const int32_t* plan_host, int P, int goal_tries, int horizon_iters,
+                                   int64_t incumbent, int64_t* cost, int32_t* i_out, int32_t* j_out, void* stream) {
+    NOT_GENERIC(e);
+    if (!e || !cost || !i_out || !j_out) return fail(LQRRT_E_ARG, "null argument");
+    TRY(incumbent_check(incumbent, -1));
+    std::vector<int> buf;
+    TRY(refine_check(e, plan_host, P, goal_tries, horizon_iters, buf));
+    *cost = incumbent; *i_out = -1; *j_out = -1;
+    TRY(refine_candidates_check(P));
+    return solo_search_run(e, horizon_iters, (hipStream_t)stream,
+                           RefineSearchSolo{{buf, P, goal_tries, horizon_iters, e->goal}, incumbent, cost, i_out, j_out});
+}
+
 extern "C" int lqrrt_refine_commit(lqrrt_engine* e, const int32_t* plan_host, int P, int goal_tries, int horizon_iters, int i, int j,
                                    int32_t* ids_out, int cap_ids, void* stream) {
     NOT_GENERIC(e);
     if (!e) return fail(LQRRT_E_ARG, "null engine");
     if (i < 0 || j <= i || j >= P) return fail(LQRRT_E_ARG, "candidate (%d, %d) outside a plan of %d nodes", i, j, P);
     if (!ids_out || cap_ids < P - 1 - j + goal_tries) return fail(LQRRT_E_ARG, "ids_out must hold %d ids", P - 1 - j + goal_tries);
-    TRY(use_device(e));
-    hipStream_t st = (hipStream_t)stream;
     std::vector<int> buf;
-    StreamDrain drain(st);                                      // (buf is the source of a copy)
-    RefineArgs a;
-    TRY(refine_prepare(e, plan_host, P, goal_tries, horizon_iters, buf, &a, st, drain));
-    const int base = e->N;
-    int* d_out = (int*)(e->d_ref_key + 1);
-    DISPATCH(e, hipLaunchKernelGGL((k_refine_commit<S>), dim3(1), dim3(64), refine_lds_bytes(e, horizon_iters), st, e->P, e->geo, e->res,
-                                   e->tv, a, i, j, base, e->fix, d_out));
-    HIPCHK(hipGetLastError());
-    return commit_finish(e, d_out, base, plan_host[i], ids_out, st, drain, "the refined chain",
-                         strf("candidate (%d, %d) does not reach the goal: nothing appended", i, j).c_str());
+    TRY(refine_check(e, plan_host, P, goal_tries, horizon_iters, buf));
+    return solo_commit_run(e, horizon_iters, plan_host[i], ids_out, (hipStream_t)stream,
+                           RefineCommitSolo{{buf, P, goal_tries, horizon_iters, e->goal}, i, j, e->res}, "the refined chain",
+                           strf("candidate (%d, %d) does not reach the goal: nothing appended", i, j).c_str());
 }
 
 // --------------------------------------------------------------------------------------------
@@ -213,7 +287,7 @@ extern "C" int lqrrt_refine_commit(lqrrt_engine* e, const int32_t* plan_host, in
 // memory -- what comes back at its head (a search's best keys; a commit's outputs and edge lengths), then a descriptor per engine
 // and the tables the descriptors point to -- staged on the host and uploaded in one copy; one launch; the head back in one copy.
 // The chunks of a call are enqueued one after another and waited for once.  The image lives in a scratch of the chunk's first
-// engine (d_refm: grown on demand, a few kB, like d_ref not part of the footprint); the calls are synchronous, so nothing reads it
+// engine (d_refm: grown on demand, a few kB, like d_solo not part of the footprint); the calls are synchronous, so nothing reads it
 // after they return.  The host images are the sources and the targets of the copies: they outlive the call's synchronise, and a
 // call that fails drains the stream before they go (StreamDrain).
 struct MultiChunk {
@@ -254,13 +328,7 @@ static std::vector<MultiChunk> multi_chunks(const std::vector<long long>& groups
 }
 
 static int refine_multi_scratch(lqrrt_engine* owner, size_t bytes, char** out) {
-    if (bytes > owner->refm_cap) {
-        if (owner->d_refm) (void)hipFree(owner->d_refm);
-        owner->d_refm = nullptr; owner->refm_cap = 0;
-        const size_t want = (bytes + 4095) / 4096 * 4096;
-        TRY(dalloc(&owner->d_refm, want));                      // (the footprint is booked at creation and in alloc_wave: this is not in it)
-        owner->refm_cap = want;
-    }
+    TRY(scratch_grow(&owner->d_refm, &owner->refm_cap, bytes));
     *out = owner->d_refm;
     return 0;
 }
@@ -305,7 +373,7 @@ static unsigned multi_grid(const MultiChunk& c, const std::vector<long long>& gr
     return retain_grid(counts, gr);
 }
 
-// A commit's image starts with what comes back: out[4] per member (commit_finish's three, padded), then room[k] edge lengths for
+// A commit's image starts with what comes back: out[4] per member (solo_commit_run's three, padded), then room[k] edge lengths for
 // every member k.
 static void multi_commit_head(MultiChunk& c, const std::vector<int>& room, Carve& carve) {
     const size_t m = c.members.size();
@@ -474,11 +542,7 @@ struct RefineSearchMulti : RefineMulti {
     static void launch(unsigned grid, size_t lds, hipStream_t st, const ProtoTable& pt, const RefineDesc* ds, const RetainGrid& gr) {
         hipLaunchKernelGGL((k_refine_search_multi<S>), dim3(grid), dim3(64), lds, st, pt, ds, gr);
     }
-    void won(int k, int, unsigned long long key) const {
-        cost[k] = (int64_t)(key >> 32);
-        i_out[k] = (int32_t)((key >> 16) & 0xffff);
-        j_out[k] = (int32_t)(key & 0xffff);
-    }
+    void won(int k, int, unsigned long long key) const { refine_decode(key, &cost[k], &i_out[k], &j_out[k]); }
 };
 
 // The replay of one candidate (ci[k], cj[k]) per engine with a winner (ci[k] >= 0).  connect_goals' commit is this one too: per

@@ -199,16 +199,13 @@ struct lqrrt_engine {
     std::vector<char> proto_cache;
     hipStream_t multi_stream = nullptr;   // the stream of the group this engine leads when a multi call runs on several host threads
 
-    // plan refinement (engine_refine.hpp): the plan's ids and cost prefix [2][ref_cap], the best key and the commit's outputs
-    int* d_ref = nullptr;
-    int ref_cap = 0;
-    unsigned long long* d_ref_key = nullptr;      // [4]: the key, then the three ints of k_refine_commit's output
+    // the one-engine search and commit calls (engine_refine.hpp: solo_scratch, the solo runners): the image of a call -- a head of 8
+    // ints (a search's best keys; a commit's three outputs at ints 2 to 4), then what the call lays out behind it: a plan with its
+    // cost prefix, waypoints, targets, the depth table and the candidate ids; grown on demand, not part of the footprint
+    char* d_solo = nullptr;
+    size_t solo_cap = 0;                          // bytes, head included
     char* d_refm = nullptr;                       // image of a multi-engine call's chunk that this engine leads (refine_multi_scratch)
     size_t refm_cap = 0;
-    // goal connection (engine_connect.hpp): 8 ints of results (the best key, then k_refine_commit's three outputs), then the depth table
-    // and the candidate ids of a search, or the one-node plan of a commit; grown on demand, like d_ref not part of the footprint
-    int* d_con = nullptr;
-    size_t con_cap = 0;                           // ints behind the 8 of the head
 
     // HBM held by this engine (lqrrt_engine_footprint): everything allocated at creation, and the H-dependent pools (alloc_wave)
     size_t bytes_fixed = 0, bytes_wave = 0, bytes_pinned = 0;

@@ -145,7 +145,8 @@ def test_fleet_connection_stays_plain_launches():
     commit = refine[refine.index("static int multi_commit_run("):refine.index("static int refine_multi_check(")]
     assert "refine_multi_scratch(" in search and "refine_multi_scratch(" in commit
     assert "multi_search_run(" in host and "multi_commit_run(" in host and "RefineCommitMulti{" in host and "k_refine_commit_multi" not in host
-    assert host.count("hipLaunchKernelGGL(") == 3                   # the solo search, the shared solo commit, the multi search
+    # the solo search and the multi search; the solo commit, like the batched one, is the refinement's (RefineCommitSolo's launch)
+    assert host.count("hipLaunchKernelGGL(") == 2 and "RefineCommitSolo{" in host and "k_refine_commit<S>" in refine
     # the chunk loop of the fleet calls is written out in the two runners and in the clearance run, nowhere else
     clear = texts["engine_clear_multi.hpp"]
     clear_run = clear[clear.index("static int clear_multi_run("):clear.index("static int clear_multi_call(")]

@@ -140,18 +140,21 @@ def test_reach_stays_plain_launches():
         assert name in src, name
     assert src.count("__launch_bounds__(64)") == 1 and "S::step(" not in src and "reach_search_body<S>(" in src
     host = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine_reach.hpp")).read()
-    assert "connect_depths(" in host and "connect_scratch(" in host
+    # the depth pass and the staging of table and id list are connect's, the scratch the solo search runner's
+    assert "connect_depths(" in host and "ReachSearchSolo h{{std::vector<int>((size_t)e->N), nodes_host, count}" in host and "return solo_search_run(" in host
     # reach adds exactly one launch site of its own, the search; its commit is the connect commit's function, which replays with
-    # k_refine_commit and adopts through the refinement's commit_finish / refine_adopt
+    # k_refine_commit (the refinement's commit hooks) and adopts through the solo commit runner / refine_adopt
     assert host.count("hipLaunchKernelGGL(") == 1 and "k_reach_search<S>" in host and "hipMalloc" not in host and "dalloc(" not in host
     assert "return connect_commit_run(" in host and "k_refine_commit" not in host
     connect = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine_connect.hpp")).read()
     shared = connect[connect.index("static int connect_commit_run("):connect.index('extern "C" int lqrrt_connect_commit(')]
-    assert "k_refine_commit<S>" in shared and "commit_finish(" in shared
+    assert "return solo_commit_run(" in shared and "RefineCommitSolo{" in shared and "hipLaunchKernelGGL(" not in shared
     assert connect.count("connect_commit_run(") == 2                # its definition and lqrrt_connect_commit's call
     refine = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "engine_refine.hpp")).read()
-    finish = refine[refine.index("static int commit_finish("):refine.index('extern "C" int lqrrt_refine_commit(')]
-    assert "refine_adopt(" in finish
+    hooks = refine[refine.index("struct RefineCommitSolo"):refine.index('extern "C" int lqrrt_refine_search(')]
+    assert hooks.count("hipLaunchKernelGGL(") == 1 and "k_refine_commit<S>" in hooks and "dim3(1)" in hooks
+    finish = refine[refine.index("static int solo_commit_run("):refine.index("static void refine_decode(")]
+    assert "solo_scratch(" in finish and "refine_adopt(" in finish and "LQRRT_E_CAPACITY" in finish and "LQRRT_E_STATE" in finish
     kernels = open(os.path.join(ROOT, "lqrrt_amd", "csrc", "kernels.hpp")).read()
     assert kernels.index('#include "connect.hpp"') < kernels.index('#include "reach.hpp"')
 
