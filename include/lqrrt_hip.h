@@ -358,6 +358,33 @@ typedef struct {
 int lqrrt_tree_clear_wait(lqrrt_engine* e, const double* tracks_host, const double* radii_host, int L, int D, int start, int waits,
                           lqrrt_clear_wait_stats* out, uint64_t* clear_host, uint64_t* dwell_host, void* stream);
 
+/* lqrrt_tree_clear against D oriented RECTANGLES instead of discs (Planner.avoid_rects; DESIGN.md section 21;
+ * tests/clear_rects_reference.py restates the rule): tracks_host [L][D][3] = world x, y and heading of rectangle d at each of L
+ * consecutive instants, extents_host [D][2] = (a, b), the half length along the heading and the half width, both >= 0.
+ * cum, tau = start + cum[pID[i]] + k, the root's one row at tau = start, table row min(tau, L - 1), first / dwell, best = the
+ * smallest (cum, id) among the hits with first == dwell == -1 and the counters are lqrrt_tree_clear's word for word, with "disc"
+ * read as "rectangle".  Only the test of one row is new:
+ *   table     per (instant, rectangle) the host derives co, so = lq_sincos(heading) (include/lqrrt_pmath.h: the function the
+ *             vehicle's own heading goes through); for the novice boats a' = a + params[18], b' = b + params[18] (the half boat
+ *             length that inflates their circles), for every other model a' = a, b' = b
+ *   points    the hull-sweeping models (BoatAdvanced, BoatIntermediate, RosBoat, Car): the hull points, placed as the static
+ *             test places them, vx = px + (c*bx + (-s)*by), vy = py + (s*bx + c*by) with c, s the row's portable cos / sin;
+ *             the novice boats: the one point (px, py)
+ *   test      dx = vx - ox; dy = vy - oy; xi = co*dx + so*dy; eta = co*dy + (-so)*dx;
+ *             inside = (fabs(xi) <= a') && (fabs(eta) <= b')      -- fp64, these operations in this order, nothing contracted
+ *   a row fails when some point is inside some rectangle of its instant.
+ * Left out on purpose: the test is geometry only -- no static map and no occupancy grid, as in lqrrt_tree_clear; the car's extra
+ * vertex at 2p is not used (it restates a quirk of the reference's circle test, and the reference has no rectangle); BoatAdvanced's
+ * planning speed box is not used (rows in a tree have passed it).  The kernel may cull rectangles conservatively; the answers are
+ * those of the test above on every (point, rectangle) pair.
+ * Reads only and synchronous, as lqrrt_tree_clear: all device memory of the call is transient.  Every argument is checked before
+ * anything is enqueued, in lqrrt_tree_clear's order: LQRRT_E_ARG for a null argument, L < 1, D < 1, start < 0, a table that is too
+ * large, an x, y or heading that is not finite, an extent that is not >= 0 and finite; LQRRT_E_STATE for a model without the path
+ * (lqrrt_tree_clear's models have it), no tree, no goal, parents that do not ascend; LQRRT_E_ARG for start + the deepest cum beyond
+ * 31 bits or hull points that do not fit in a workgroup's LDS (the launch reserves exactly 16 V bytes). */
+int lqrrt_tree_clear_rects(lqrrt_engine* e, const double* tracks_host /*[L][D][3]*/, const double* extents_host /*[D][2]*/,
+                           int L, int D, int start, lqrrt_clear_stats* out, int32_t* first_host, int32_t* dwell_host, void* stream);
+
 /* lqrrt_tree_clear and lqrrt_tree_clear_wait for n engines at once (lqrrt_amd.avoids, deconflict(batched=True): a fleet that
  * checks its plans every tick against tracked traffic).  The rule is the one stated above (DESIGN.md sections 16 and 17),
  * unchanged: member k's out[k] and per-node arrays are exactly what the one-tree call on engines[k] with tracks_host[k],

@@ -283,6 +283,56 @@ class Engine(object):
         Reads only: tree, goal bookkeeping and footprint stay as they are."""
         return self._clear("lqrrt_tree_clear", nat.ClearStats, np.int32, tracks, radii, start, None, per_node)
 
+    @staticmethod
+    def rect_table(tracks, extents, start=0):
+        """(tracks [L][D][3], extents [D][2], start) as lqrrt_tree_clear_rects takes them, or ValueError.  `tracks` is an array
+        (L, D, 3) -- world x, y and heading of D rectangles at L consecutive instants -- or a list of D arrays (L_d, 3), each padded
+        to the longest by holding its last row; `extents` is one (half length, half width) for all, or one pair per rectangle.
+        Host only."""
+        if isinstance(tracks, (list, tuple)):
+            rows = [np.asarray(t, dtype=np.float64) for t in tracks]
+            if len(rows) < 1 or any(t.ndim != 2 or t.shape[1] != 3 or len(t) < 1 for t in rows):
+                raise ValueError("Expected tracks as an array (L, D, 3) or a list of D >= 1 arrays (L_d >= 1, 3).")
+            L = max(len(t) for t in rows)
+            table = np.empty((L, len(rows), 3))
+            for d, t in enumerate(rows):
+                table[:len(t), d] = t
+                table[len(t):, d] = t[-1]                         # a track that has ended stays where it ended
+        else:
+            table = np.ascontiguousarray(tracks, dtype=np.float64)
+        if table.ndim != 3 or table.shape[2] != 3 or table.shape[0] < 1 or table.shape[1] < 1:
+            raise ValueError("Expected tracks as an array (L, D, 3) with L >= 1 and D >= 1, or a list of D arrays (L_d, 3).")
+        if not np.all(np.isfinite(table)):
+            raise ValueError("A track position or heading is not finite.")
+        D = table.shape[1]
+        ext = np.asarray(extents, dtype=np.float64)
+        if ext.shape not in [(2,), (D, 2)]:
+            raise ValueError("Expected extents to be one (half length, half width), or one pair per rectangle (%d)." % D)
+        ext = np.ascontiguousarray(np.broadcast_to(ext, (D, 2)))
+        if not (np.all(ext >= 0) and np.all(np.isfinite(ext))):
+            raise ValueError("An extent must be >= 0 and finite.")
+        if int(start) != start or int(start) < 0:
+            raise ValueError("start must be an integer >= 0.")
+        return np.ascontiguousarray(table), ext, int(start)
+
+    def tree_clear_rects(self, tracks, extents, start=0, per_node=False):
+        """tree_clear against moving oriented rectangles (lqrrt_tree_clear_rects; the rule: tests/clear_rects_reference.py).
+        `tracks`, `extents`: what rect_table takes -- the rectangles' x, y and heading at consecutive instants spaced by the
+        engine's dt, and their half length (along the heading) and half width; row `start` of the table coincides with the root's
+        row.  Returns what tree_clear returns: the counters, and with `per_node` also first [N] and dwell_first [N] (int32).
+        Reads only: tree, goal bookkeeping and footprint stay as they are."""
+        table, ext, start = self.rect_table(tracks, extents, start)
+        st = nat.ClearStats()
+        a = b = None
+        if per_node:
+            n = max(self.size, 1)
+            a, b = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        nat.check(nat.lib().lqrrt_tree_clear_rects(self.h, nat.ptr(table), nat.ptr(ext), table.shape[0], table.shape[1], start, C.byref(st),
+                                                   None if a is None else nat.ptr(a), None if b is None else nat.ptr(b), self._stream()))
+        if per_node:
+            return st.as_dict(), a[:st.size], b[:st.size]
+        return st.as_dict()
+
     def tree_clear_connect(self, tracks, radii, start, horizon_iters, tries=8, nodes=None, per_node=False):
         """tree_clear and connect_search in one native call (lqrrt_tree_clear_connect; the rule: tests/clear_connect_reference.py):
         besides tree_clear's answer, the node whose root path is clear of the discs and whose goal chain -- up to `tries` steers at

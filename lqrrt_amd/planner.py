@@ -821,7 +821,8 @@ class Planner:
         finish_on_goal tail is not applied to it, because it would not have been checked.  Otherwise the plan is untouched.
         The tree is never modified (but for `connect`, below).  Returns None when there is no tree of this planner on the device
         (refine_plan's condition).  Not covered: chains that connect_goal / connect_via / retarget appended are tested like any
-        other edge, but without `connect` nothing is appended here; waiting anywhere but at the start; obstacles that are not discs.
+        other edge, but without `connect` nothing is appended here; waiting anywhere but at the start; obstacles that are not discs
+        (see avoid_rects).
 
         `max_wait` in 1 .. 63 also asks "and if I left later?": the vehicle may stand on the plan's first row (the root's) for
         w = 0 .. max_wait rows of dt and follow the tree w rows later; while it stands there the root's row is tested at every
@@ -873,6 +874,30 @@ class Planner:
                 first = dwell = None
             else:                                                   # the time of its first conflict: the plain query, once
                 _, first, dwell = self._engine.tree_clear(table, radii, start + self.plan_wait, per_node=True)
+        return self._avoid_end(run, out, first, dwell, start, adopt)
+
+    def avoid_rects(self, tracks, extents, start=0, adopt=True):
+        """
+        avoid against obstacles that are oriented rectangles -- other hulls: a 6 m x 0.4 m vessel is covered by a disc of 3 m
+        radius, and two of them can then never pass in a channel.  `tracks` gives world x, y and heading of D rectangles at
+        consecutive instants spaced by `dt`: an array (L, D, 3), or a list of D arrays (L_d, 3), each held at its last row once it
+        has ended; `extents` is (half length along the heading, half width), one pair for all or one per rectangle; `start` is
+        avoid's.  Time, the wait at the goal, the best plan, the dict (size, conflicts, blocked, hits, clear_hits, best_end,
+        best_steps, plan_first), adoption and the refusals are avoid's; only the test of one row differs: the hull points of the
+        row's pose (the novice boats: its centre, against extents grown by half the boat length) against the rectangles of its
+        instant, point in rectangle with the edge included.  It is geometry only: no static map, not the car's vertex at 2p, not
+        BoatAdvanced's planning speed box.  One call on the device (csrc/clear_rects.hpp); tests/clear_rects_reference.py restates
+        the rule.  The tree is never modified.  Returns None when there is no tree of this planner on the device.  Not covered
+        (DESIGN.md section 21): max_wait, connect, a fleet launch, discs and rectangles in one call, convex polygons.
+        """
+        if self.callback_mode:                                      # (as avoid)
+            raise NotImplementedError("avoid_rects: in callback mode the feasibility test is the user's Python function; the device "
+                                      "cannot call it on the rows of the tree.")
+        table, extents, start = Engine.rect_table(tracks, extents, start)
+        run = self._avoid_begin()
+        if run is None:
+            return None
+        out, first, dwell = self._engine.tree_clear_rects(table, extents, start, per_node=True)
         return self._avoid_end(run, out, first, dwell, start, adopt)
 
     # The parts of avoid that it shares with avoids and deconflict(batched=True), which make the device calls for several planners
@@ -1546,7 +1571,7 @@ def retargets(planners, goals, goal_tries=8, nodes=None, finish_on_goal=None):
     return results
 
 
-def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False, connect=0):
+def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False, connect=0, extents=None):
     """
     Prioritised planning over the trees as they stand: in `order` (default: as listed) every planner picks, with Planner.avoid, the
     best plan of its tree that stays clear of the plans of the planners before it -- each of those a disc of its radius that moves
@@ -1580,6 +1605,11 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False, 
     `connect` with batched=True -- a chain candidate has no rows in any tree until it is committed, and the rounds adopt only at
     the end -- and `connect` together with `max_wait`, as in avoid.
 
+    `extents` = (half length, half width), one pair for every vehicle or one per planner (n, 2), makes every earlier planner an
+    oriented RECTANGLE instead of a disc: it moves along its plan's x_seq[:, :3] -- x, y and heading, state index 2 -- and then sits
+    where it arrived, and every planner asks Planner.avoid_rects.  `radii` must then be None.  Sequential form only: with `extents`,
+    `max_wait`, batched=True and `connect` are not covered and refused with ValueError.  Without `extents` nothing changes.
+
     Refused with ValueError before any planner is touched: planners that do not share `dt`, a planner twice, an `order` that is no
     permutation, `radii` of the wrong shape or negative, a `max_wait` that is no integer in 0 .. 63, a planner without a plan (it
     cannot be a track).  Callback mode raises
@@ -1592,12 +1622,25 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False, 
         raise ValueError("deconflict: order must be a permutation of the planners' indices.")
     if len(set(id(p) for p in planners)) != n:
         raise ValueError("deconflict: a planner appears twice.")
-    r = np.asarray(radii, dtype=np.float64)
-    if r.shape not in [(), (n,)]:
-        raise ValueError("deconflict: expected one radius, or one per planner.")
-    r = np.broadcast_to(r, (n,))
-    if not np.all(r >= 0):
-        raise ValueError("deconflict: a radius must be >= 0.")
+    if extents is not None:
+        if radii is not None:
+            raise ValueError("deconflict: with extents the vehicles are rectangles; radii must be None.")
+        ext = np.asarray(extents, dtype=np.float64)
+        if ext.shape not in [(2,), (n, 2)]:
+            raise ValueError("deconflict: expected extents as one (half length, half width), or one pair per planner.")
+        ext = np.broadcast_to(ext, (n, 2))
+        if not (np.all(ext >= 0) and np.all(np.isfinite(ext))):
+            raise ValueError("deconflict: an extent must be >= 0 and finite.")
+        if max_wait != 0 or batched or connect != 0:
+            raise ValueError("deconflict: with extents, max_wait, batched=True and connect are not covered.")
+        r = np.zeros(n)
+    else:
+        r = np.asarray(radii, dtype=np.float64)
+        if r.shape not in [(), (n,)]:
+            raise ValueError("deconflict: expected one radius, or one per planner.")
+        r = np.broadcast_to(r, (n,))
+        if not np.all(r >= 0):
+            raise ValueError("deconflict: a radius must be >= 0.")
     if int(start) != start or int(start) < 0:
         raise ValueError("deconflict: start must be an integer >= 0.")
     max_wait = Engine.wait_count(max_wait, "deconflict: max_wait", 0, 63)
@@ -1622,6 +1665,10 @@ def deconflict(planners, radii, order=None, start=0, max_wait=0, batched=False, 
         if at == 0:
             continue
         before = order[:at]
+        if extents is not None:
+            tracks = [np.asarray(planners[j].x_seq, dtype=np.float64)[:, :3] for j in before]
+            results[k] = planners[k].avoid_rects(tracks, ext[before], start)
+            continue
         tracks = [np.asarray(planners[j].x_seq, dtype=np.float64)[:, :2] for j in before]
         results[k] = planners[k].avoid(tracks, r[before], start, max_wait=max_wait, connect=connect)
     return results
