@@ -299,7 +299,8 @@ static int commit_finish(lqrrt_engine* e, int W, bool fused, int64_t max_commit,
         if (!e->sync_mode) {
             e->chain_depth.assign((size_t)C, 0);
             for (int t = 0; t < C; ++t) {
-                if (len[t] > 0 && par[t] < 0 && ~par[t] < t) e->chain_depth[t] = e->chain_depth[~par[t]] + 1;
+                // (a rejected sample counts too: its rollout had to start from the in-wave parent to find that it records no row)
+                if (par[t] < 0 && ~par[t] < t) e->chain_depth[t] = e->chain_depth[~par[t]] + 1;
                 deepest = std::max(deepest, e->chain_depth[t]);
             }
         }
