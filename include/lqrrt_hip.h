@@ -385,6 +385,22 @@ int lqrrt_tree_clear_wait(lqrrt_engine* e, const double* tracks_host, const doub
 int lqrrt_tree_clear_rects(lqrrt_engine* e, const double* tracks_host /*[L][D][3]*/, const double* extents_host /*[D][2]*/,
                            int L, int D, int start, lqrrt_clear_stats* out, int32_t* first_host, int32_t* dwell_host, void* stream);
 
+/* lqrrt_tree_clear_rects for `waits` departure delays at once (Planner.avoid_rects with max_wait; DESIGN.md section 22;
+ * tests/clear_rects_wait_reference.py restates the rule).  Nothing is new: the rule is lqrrt_tree_clear_wait's comment above --
+ * wait, edges, clear, dwell_ok, best, the counters of lqrrt_clear_wait_stats -- with "the row test" read as the test of
+ * lqrrt_tree_clear_rects's comment above: table, points and test as stated there, geometry only, what is left out there left out
+ * here.  tracks_host, extents_host, L, D, start are lqrrt_tree_clear_rects's; waits, out, clear_host, dwell_host are
+ * lqrrt_tree_clear_wait's.  Bit w of clear[i] is therefore (first[i] == -1 of lqrrt_tree_clear_rects at start + w) && root_ok bit
+ * w, where root_ok bit w = the root's row passes at every tau = start .. start + w, and bit w of dwell_ok[i] is (dwell[i] == -1 of
+ * that call), 0 for a node that is no hit.  One call replaces `waits` calls of lqrrt_tree_clear_rects and the test of the root's
+ * row during the wait.  Reads only and synchronous: all device memory of the call is transient (92 bytes per node and the table).
+ * Every argument is checked before anything is enqueued: lqrrt_tree_clear_rects's refusals in their order, with LQRRT_E_ARG for
+ * waits outside 1 .. 64 behind the extents, LQRRT_E_ARG when start + (waits - 1) + the deepest cum goes beyond 31 bits, and the
+ * hull points' 16 V bytes + 64 against a workgroup's LDS. */
+int lqrrt_tree_clear_rects_wait(lqrrt_engine* e, const double* tracks_host /*[L][D][3]*/, const double* extents_host /*[D][2]*/,
+                                int L, int D, int start, int waits, lqrrt_clear_wait_stats* out, uint64_t* clear_host,
+                                uint64_t* dwell_host, void* stream);
+
 /* lqrrt_tree_clear and lqrrt_tree_clear_wait for n engines at once (lqrrt_amd.avoids, deconflict(batched=True): a fleet that
  * checks its plans every tick against tracked traffic).  The rule is the one stated above (DESIGN.md sections 16 and 17),
  * unchanged: member k's out[k] and per-node arrays are exactly what the one-tree call on engines[k] with tracks_host[k],

@@ -16,6 +16,7 @@ struct ClearRects {
     typedef ClearOut Out;
     typedef lqrrt_clear_stats Stats;
     static constexpr const char* NAME = "lqrrt_tree_clear_rects";
+    static constexpr const char* WAIT_TERM = "";
     static constexpr size_t CHECK_LDS = 0, HIT_BYTES = 0;
     template <class S>
     static void check(const lqrrt_engine* e, const ClearBufs<ClearRects>& d, int N, int L, int D, int start, int, size_t hull_bytes, hipStream_t st) {
@@ -29,9 +30,11 @@ struct ClearRects {
     static void stats(const ClearOut& h, const std::vector<long long>& cum, int N, lqrrt_clear_stats* out) { ClearPlain::stats(h, cum, N, out); }
 };
 
-// Every argument of the call, before anything is allocated or enqueued.  Fills cum (as clear_check) and the table.
+// Every argument of the call, before anything is allocated or enqueued.  Fills cum (as clear_check) and the table.  `C`: the
+// call's traits (engine_clear_rects_wait.hpp has the other one); `waits`: 1 for lqrrt_tree_clear_rects.
+template <class C = ClearRects>
 static int clear_rects_check(lqrrt_engine* e, const void* out, const double* tracks_host, const double* extents_host, int L, int D, int start,
-                             std::vector<long long>& cum, std::vector<double>& table) {
+                             std::vector<long long>& cum, std::vector<double>& table, int waits = 1) {
     if (!e || !out || !tracks_host || !extents_host) return fail(LQRRT_E_ARG, "null argument");
     if (L < 1 || D < 1) return fail(LQRRT_E_ARG, "the track table needs L >= 1 instants and D >= 1 rectangles (L = %d, D = %d)", L, D);
     if (start < 0) return fail(LQRRT_E_ARG, "start must be >= 0 (%d)", start);
@@ -42,12 +45,13 @@ static int clear_rects_check(lqrrt_engine* e, const void* out, const double* tra
     for (int d = 0; d < 2 * D; ++d)
         if (!(extents_host[d] >= 0.0) || !std::isfinite(extents_host[d]))
             return fail(LQRRT_E_ARG, "half %s %d is not >= 0 and finite", d % 2 ? "width" : "length", d / 2);
+    if (waits < 1 || waits > 64) return fail(LQRRT_E_ARG, "waits must be 1 .. 64 delays (%d): the answers are 64-bit masks", waits);
     bool discs = false;
     DISPATCH(e, discs = has_discs<S>::value);
-    if (!discs) return fail(LQRRT_E_STATE, "%s: the feasibility test of model %d has no circle path", ClearRects::NAME, e->model);
+    if (!discs) return fail(LQRRT_E_STATE, "%s: the feasibility test of model %d has no circle path", C::NAME, e->model);
     if (!e->has_res || e->N < 1) return fail(LQRRT_E_STATE, "no tree to check: set_resolution and tree_reset / tree_load first");
     if (!e->has_goal) return fail(LQRRT_E_STATE, "no goal: lqrrt_engine_set_resolution with has_goal first");
-    // start + the deepest cum fits 31 bits
+    // start + the longest wait + the deepest cum fits 31 bits
     const int N = e->N;
     cum.resize((size_t)N);
     if (e->h_elen[0] < 1) return fail(LQRRT_E_STATE, "the root's edge has no row");
@@ -60,9 +64,10 @@ static int clear_rects_check(lqrrt_engine* e, const void* out, const double* tra
         cum[(size_t)v] = cum[(size_t)p] + e->h_elen[(size_t)v];
         deepest = std::max(deepest, cum[(size_t)v]);
     }
-    if ((long long)start + deepest > 0x7fffffffLL) return fail(LQRRT_E_ARG, "start + the deepest node's steps leave 31 bits");
+    if ((long long)start + (waits - 1) + deepest > 0x7fffffffLL)
+        return fail(LQRRT_E_ARG, "start%s + the deepest node's steps leave 31 bits", C::WAIT_TERM);
     const size_t hull_bytes = sizeof(double) * (size_t)2 * e->geo.V;
-    if (e->lds_limit && hull_bytes + ClearRects::CHECK_LDS > e->lds_limit)
+    if (e->lds_limit && hull_bytes + C::CHECK_LDS > e->lds_limit)
         return fail(LQRRT_E_ARG, "the clearance check stages the hull points in LDS: 16 V = %zu bytes (V = %d), the device's limit is %zu",
                     hull_bytes, e->geo.V, e->lds_limit);
     const double inflate = model_novice(e->model) ? e->P.p[18] : 0.0;

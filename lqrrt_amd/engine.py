@@ -377,6 +377,26 @@ class Engine(object):
         hit).  Reads only: tree, goal bookkeeping and footprint stay as they are."""
         return self._clear("lqrrt_tree_clear_wait", nat.ClearWaitStats, np.uint64, tracks, radii, start, waits, per_node)
 
+    def tree_clear_rects_wait(self, tracks, extents, start=0, waits=1, per_node=False):
+        """tree_clear_wait against moving oriented rectangles (lqrrt_tree_clear_rects_wait; the rule:
+        tests/clear_rects_wait_reference.py): tree_clear_rects for the departure delays w = 0 .. waits - 1 at once, 1 <= waits <= 64,
+        the root's row tested at every instant of the wait.  `tracks`, `extents`, `start`: what rect_table takes.  Returns what
+        tree_clear_wait returns: its counters, and with `per_node` also clear [N] and dwell_ok [N] (uint64 masks over the delays).
+        Reads only: tree, goal bookkeeping and footprint stay as they are."""
+        table, ext, start = self.rect_table(tracks, extents, start)
+        waits = self.wait_count(waits)
+        st = nat.ClearWaitStats()
+        a = b = None
+        if per_node:
+            n = max(self.size, 1)
+            a, b = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
+        nat.check(nat.lib().lqrrt_tree_clear_rects_wait(self.h, nat.ptr(table), nat.ptr(ext), table.shape[0], table.shape[1], start, waits,
+                                                        C.byref(st), None if a is None else nat.ptr(a), None if b is None else nat.ptr(b),
+                                                        self._stream()))
+        if per_node:
+            return st.as_dict(), a[:st.size], b[:st.size]
+        return st.as_dict()
+
     def _clear(self, call, stats, dtype, tracks, radii, start, waits, per_node):
         """tree_clear (`waits` None) and tree_clear_wait: the arguments checked in their order, the counters, and with `per_node`
         the call's two arrays [N] of `dtype`."""

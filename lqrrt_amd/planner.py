@@ -876,7 +876,7 @@ class Planner:
                 _, first, dwell = self._engine.tree_clear(table, radii, start + self.plan_wait, per_node=True)
         return self._avoid_end(run, out, first, dwell, start, adopt)
 
-    def avoid_rects(self, tracks, extents, start=0, adopt=True):
+    def avoid_rects(self, tracks, extents, start=0, adopt=True, max_wait=0):
         """
         avoid against obstacles that are oriented rectangles -- other hulls: a 6 m x 0.4 m vessel is covered by a disc of 3 m
         radius, and two of them can then never pass in a channel.  `tracks` gives world x, y and heading of D rectangles at
@@ -887,17 +887,34 @@ class Planner:
         row's pose (the novice boats: its centre, against extents grown by half the boat length) against the rectangles of its
         instant, point in rectangle with the edge included.  It is geometry only: no static map, not the car's vertex at 2p, not
         BoatAdvanced's planning speed box.  One call on the device (csrc/clear_rects.hpp); tests/clear_rects_reference.py restates
-        the rule.  The tree is never modified.  Returns None when there is no tree of this planner on the device.  Not covered
-        (DESIGN.md section 21): max_wait, connect, a fleet launch, discs and rectangles in one call, convex polygons.
+        the rule.  The tree is never modified.  Returns None when there is no tree of this planner on the device.
+
+        `max_wait` in 1 .. 63 is avoid's: the vehicle may stand on the plan's first row for w = 0 .. max_wait rows of dt, tested
+        there against the rectangles at every instant of the wait, and follow the tree w rows later -- in a channel the answer
+        to an oncoming hull is often "hold the berth two ticks, then take the short branch".  All delays are answered by one call
+        on the device (csrc/clear_rects_wait.hpp; tests/clear_rects_wait_reference.py restates the rule); the best plan, the dict
+        (size, hits, clear_hits, clear_now, best_end, best_wait, best_steps, best_arrival, plan_first), the adoption with
+        `best_wait` copies of the first row in front and `plan_wait`, and the one more plain call for plan_first when the current
+        plan does not hold are avoid's with max_wait.  With max_wait = 0 the call, its cost and its dict are what they were.
+        Not covered (DESIGN.md sections 21 and 22): connect, a fleet launch, deconflict(extents=...) with max_wait, discs and
+        rectangles in one call, convex polygons.
         """
         if self.callback_mode:                                      # (as avoid)
             raise NotImplementedError("avoid_rects: in callback mode the feasibility test is the user's Python function; the device "
                                       "cannot call it on the rows of the tree.")
         table, extents, start = Engine.rect_table(tracks, extents, start)
+        max_wait = Engine.wait_count(max_wait, "max_wait", 0, 63)
         run = self._avoid_begin()
         if run is None:
             return None
-        out, first, dwell = self._engine.tree_clear_rects(table, extents, start, per_node=True)
+        if max_wait == 0:
+            out, first, dwell = self._engine.tree_clear_rects(table, extents, start, per_node=True)
+        else:
+            out, clear, dwell_ok = self._engine.tree_clear_rects_wait(table, extents, start, max_wait + 1, per_node=True)
+            if self._avoid_plan_holds(run, clear, dwell_ok, max_wait):
+                first = dwell = None
+            else:                                                   # the time of its first conflict: the plain query, once
+                _, first, dwell = self._engine.tree_clear_rects(table, extents, start + self.plan_wait, per_node=True)
         return self._avoid_end(run, out, first, dwell, start, adopt)
 
     # The parts of avoid that it shares with avoids and deconflict(batched=True), which make the device calls for several planners
