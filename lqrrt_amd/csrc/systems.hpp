@@ -307,9 +307,16 @@ struct BoatCommon {
     __device__ __forceinline__ static bool torque_direct(double vmin2, const double* x) {
         return x[3] >= 0.0 && x[3] * x[3] + x[4] * x[4] > vmin2;
     }
+    // The world-frame velocity R(h) v as the reference's R[:2, :2].dot(x[3:5]) sums it: from +0.  For every velocity but zero
+    // the leading term changes no bit; a velocity of signed zeros comes out as (+0, +0) whatever its signs and the heading, so
+    // atan2 gives 0 and the torque is the reference's gain * wrap(-h) -- not half a turn for v = (-0, +0).
+    __device__ __forceinline__ static void world_velocity(const double* x, double c, double s, double& vw0, double& vw1) {
+        vw0 = (0.0 + c * x[3]) + (-s) * x[4];
+        vw1 = (0.0 + s * x[3]) + c * x[4];
+    }
     __device__ __forceinline__ static double rudder_ref(double gainv, const double* x, double c, double s) {
-        const double vw0 = c * x[3] + (-s) * x[4];
-        const double vw1 = s * x[3] + c * x[4];
+        double vw0, vw1;
+        world_velocity(x, c, s, vw0, vw1);
         const double ang = lq_atan2(vw1, vw0);
         double cg, sg;
         lq_sincos(ang, &sg, &cg);
@@ -494,8 +501,8 @@ struct BoatAdvanced : BoatCommon {
                                        const double* trig, const double* K, double dt, int lane,
                                        double* e, double* u, double* xn, double* trn) {
         const double c = trig[0], s = trig[1];
-        const double vw0 = c * x[3] + (-s) * x[4];
-        const double vw1 = s * x[3] + c * x[4];
+        double vw0, vw1;
+        world_velocity(x, c, s, vw0, vw1);
         double rud;
         packed_erf_effort(P[37], xt, ttrig, x, trig, K, dt, lane, vw1, vw0, torque_direct(P[52], x), e, u, rud, trn);
         double uc[3] = {u[0], u[1], u[2] + rud};
@@ -604,8 +611,8 @@ struct BoatIntermediate : BoatCommon {
                                        const double* trig, const double* K, double dt, int lane,
                                        double* e, double* u, double* xn, double* trn) {
         const double c = trig[0], s = trig[1];
-        const double vw0 = c * x[3] + (-s) * x[4];
-        const double vw1 = s * x[3] + c * x[4];
+        double vw0, vw1;
+        world_velocity(x, c, s, vw0, vw1);
         double rud;
         packed_erf_effort(P[12], xt, ttrig, x, trig, K, dt, lane, vw1, vw0, torque_direct(P[21], x), e, u, rud, trn);
         double uc[3] = {u[0], u[1], u[2] + rud};
@@ -703,7 +710,7 @@ struct RosBoat : BoatCommon {
         const double c = trig[0], s = trig[1];
         double yb, xb;
         if (rmode == 1) { yb = P[40] - x[1]; xb = P[39] - x[0]; }
-        else { xb = c * x[3] + (-s) * x[4]; yb = s * x[3] + c * x[4]; }
+        else world_velocity(x, c, s, xb, yb);
         double rud;
         packed_erf_effort(P[37], xt, ttrig, x, trig, K, dt, lane, yb, xb, rmode == 2 && torque_direct(P[49], x), e, u, rud, trn);
         double uc[3] = {u[0], u[1], rud};           // both behaviours REPLACE the yaw effort (boat.py:42, car.py:43)

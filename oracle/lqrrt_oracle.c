@@ -308,7 +308,9 @@ static void gain(const orc* o, const double* x, const double* tr, const double* 
  *   v = 0           atan2 of signed zeros, where the reference's form gives wrap(-h). */
 static double rudder_term(double g, double vmin2, const double* x, double c, double s) {
     if (x[3] >= 0.0 && x[3] * x[3] + x[4] * x[4] > vmin2) return g * lq_atan2(x[4], x[3]);
-    const double vw0 = c * x[3] + (-s) * x[4], vw1 = s * x[3] + c * x[4];
+    /* R(h) v summed from +0, as the reference's R[:2, :2].dot(x[3:5]) sums it: a velocity of signed zeros gives (+0, +0) whatever
+     * its signs, so atan2 gives 0 and the torque is g * wrap(-h); no other velocity changes a bit (systems.hpp world_velocity) */
+    const double vw0 = (0.0 + c * x[3]) + (-s) * x[4], vw1 = (0.0 + s * x[3]) + c * x[4];
     const double ang = lq_atan2(vw1, vw0);
     double cg, sg;
     lq_sincos(ang, &sg, &cg);

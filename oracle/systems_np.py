@@ -292,7 +292,9 @@ class BoatNovice(_HeadingSystem):
 
 
 class RosBoat(_HeadingSystem):
-    """demos/lqrrt_ros/behaviors/{params,boat,car,escape}.py: one boat, three behaviours."""
+    """demos/lqrrt_ros/behaviors/{params,boat,car,escape}.py: one boat, three behaviours.  What a behaviour selects is kept in
+    rudder_mode (0 none, 1 stare at the focus point, 2 along the velocity), sat_mode (0 even down-scaling, 1 per-thruster clip) and
+    no_reverse, the words of lqrrt_amd.systems.RosBoat, so that a test can cross the rules of two behaviours."""
     nstates, ncontrols = 6, 3
     plan_kwargs = dict(horizon=(0.1, 3), dt=0.1, FPR=0)     # params.py:31-33
 
@@ -319,13 +321,14 @@ class RosBoat(_HeadingSystem):
         real_tol = [0.5, 0.5, np.deg2rad(10), np.inf, np.inf, np.inf]
         free_radius = 6
         self.Smat = np.diag([1, 1, 1, 1, 1, 1])
+        self.rudder, self.rudder_mode, self.sat_mode, self.no_reverse = 0, 0, 0, 0
         if behavior == "boat":
-            self.rudder = 8000
+            self.rudder, self.rudder_mode = 8000, (1 if focus is not None else 0)
             self.kp, self.kd = np.diag([250, 250, 2500]), np.diag([5, 5, 0.001])
             self.goal_buffer = [real_tol[0], real_tol[1], real_tol[2], 10, 10, 6]
             self.error_tol = np.copy(self.goal_buffer)
         elif behavior == "car":
-            self.rudder = 6000
+            self.rudder, self.rudder_mode, self.sat_mode, self.no_reverse = 6000, 2, 1, 1
             self.kp, self.kd = np.diag([150, 150, 0]), np.diag([150, 5, 0])
             self.Smat = np.diag([1, 1, 1, 0, 0, 0])
             self.goal_buffer = [0.5 * free_radius, 0.5 * free_radius, np.inf, np.inf, np.inf, np.inf]
@@ -354,13 +357,13 @@ class RosBoat(_HeadingSystem):
     def dynamics(self, x, u, dt):
         R = rot3(x[2])
         D = np.where(x[3:] >= 0, self.D_pos, self.D_neg)
-        if self.behavior == "boat" and self.focus is not None:          # boat.py:34-42
+        if self.rudder_mode == 1:                                       # boat.py:34-42
             vec = self.focus[:2] - x[:2]
             u[2] = self.rudder * wrap_err(np.arctan2(vec[1], vec[0]), x[2])
-        elif self.behavior == "car":                                    # car.py:36-43
+        elif self.rudder_mode == 2:                                     # car.py:36-43
             vw = R[:2, :2].dot(x[3:5])
             u[2] = self.rudder * wrap_err(np.arctan2(vw[1], vw[0]), x[2])
-        if self.behavior == "car":                                      # car.py:46
+        if self.sat_mode == 1:                                          # car.py:46
             u = self.B.dot(np.clip(self.invB.dot(u), -self.thrust_max, self.thrust_max))
         else:                                                           # boat.py:44-48 / escape.py:32-36
             thrusts = self.invB.dot(u)
@@ -369,7 +372,7 @@ class RosBoat(_HeadingSystem):
                 u = self.B.dot(np.min(ratios) * thrusts)
         xdot = np.concatenate((R.dot(x[3:]), self.invM * (u - D * x[3:])))
         xn = x + xdot * dt
-        if self.behavior == "car" and xn[3] < 0:                        # car.py:54-56
+        if self.no_reverse and xn[3] < 0:                               # car.py:54-56
             xn[3] = abs(x[3])
         return xn
 

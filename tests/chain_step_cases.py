@@ -97,6 +97,20 @@ def directed_table(vps, O):
 
 # ---------------------------------------------------------------------------------------------------- the step, restated
 
+def wrap_libm(ang, h):
+    """wrap_err(ang, h) with libm: the angle from heading h to direction ang."""
+    c, s = math.cos(h), math.sin(h)
+    return math.atan2(math.sin(ang) * c - math.cos(ang) * s, math.cos(ang) * c + math.sin(ang) * s)
+
+
+def rudder_libm(rudder, vmin2, x):
+    """BoatCommon::rudder_term with libm."""
+    if x[3] >= 0.0 and x[3] * x[3] + x[4] * x[4] > vmin2:
+        return rudder * math.atan2(x[4], x[3])
+    c, s = math.cos(x[2]), math.sin(x[2])
+    return rudder * wrap_libm(math.atan2(s * x[3] + c * x[4], c * x[3] - s * x[4]), x[2])
+
+
 class Model(object):
     """The parameters of csrc/systems.hpp BoatAdvanced and its per-step predicates."""
 
@@ -113,11 +127,7 @@ class Model(object):
 
     def torque(self, x):
         """The heading torque with libm (categories that use it keep a margin)."""
-        if self.direct(x):
-            return self.rudder * math.atan2(x[4], x[3])
-        c, s = math.cos(x[2]), math.sin(x[2])
-        ang = math.atan2(s * x[3] + c * x[4], c * x[3] - s * x[4])
-        return self.rudder * math.atan2(math.sin(ang) * c - math.cos(ang) * s, math.cos(ang) * c + math.sin(ang) * s)
+        return rudder_libm(self.rudder, self.vmin2, x)
 
     def thrusts(self, x, u):
         """invB (u + torque) before the clip."""
@@ -134,23 +144,22 @@ class Model(object):
         return not any(x[3 + i] > self.vmax[i] or x[3 + i] < self.vmin[i] for i in range(3))
 
 
-def step_labels(m, x, u):
-    """Categories of ONE step evaluated at state x with effort u = K e."""
+def torque_labels(vmin2, x):
+    """Which arm of BoatCommon::rudder_term runs at state x, and where inside lq_atan2 the one-atan2 arm lands."""
     out = set()
     vx, vy = float(x[3]), float(x[4])
     v2 = vx * vx + vy * vy
-    # ---- torque arm
     if vx < 0.0:
         out.add("torque:vx<0")
     elif vx == 0.0 and vy == 0.0:
         out.add("torque:v=-0" if (math.copysign(1.0, vx) < 0 or math.copysign(1.0, vy) < 0) else "torque:v=+0")
-    elif v2 <= m.vmin2:
+    elif v2 <= vmin2:
         out.add("torque:slow")
-        if v2 == m.vmin2:
+        if v2 == vmin2:
             out.add("torque:on-vmin2")
-    if m.direct(x):
+    if vx >= 0.0 and v2 > vmin2:                               # torque_direct
         out.add("torque:direct")
-        if v2 == up(m.vmin2):
+        if v2 == up(vmin2):
             out.add("torque:vmin2+1ulp")
         ax, ay = abs(vx), abs(vy)
         if ay > ax:
@@ -163,26 +172,69 @@ def step_labels(m, x, u):
         out.add("torque:t>tan(pi/8)" if t > TAN_PI_8 else "torque:t<=tan(pi/8)")
     else:
         out.add("torque:reference")
-    # ---- lane rows: thrusters, drag, car-like rule
-    t = m.thrusts(x, u)
-    hi = [t[j] > m.tmax[j] * (1 + 1e-6) for j in range(4)]
-    lo = [t[j] < -m.tmax[j] * (1 + 1e-6) for j in range(4)]
-    inside = [abs(t[j]) < m.tmax[j] * (1 - 1e-6) for j in range(4)]
+    return out
+
+
+def thruster_labels(t, tmax):
+    """One thruster beyond its limit alone, or none (1e-6 either side of the limit: libm's last bits cannot cross it)."""
+    out = set()
+    hi = [t[j] > tmax[j] * (1 + 1e-6) for j in range(4)]
+    lo = [t[j] < -tmax[j] * (1 + 1e-6) for j in range(4)]
+    inside = [abs(t[j]) < tmax[j] * (1 - 1e-6) for j in range(4)]
     for j in range(4):
         if (hi[j] or lo[j]) and all(inside[k] for k in range(4) if k != j):
             out.add("thruster%d:%s-alone" % (j, "upper" if hi[j] else "lower"))
     if all(inside):
         out.add("thrusters:none-saturated")
-    for i in range(3):
-        out.add("drag%d:%s" % (i, "v>=0" if x[3 + i] >= 0.0 else "v<0"))
-    out.add("carlike:x3>0" if vx > 0.0 else "carlike:x3<0" if vx < 0.0 else "carlike:x3==0")
     return out
 
 
+def drag_labels(x):
+    return {"drag%d:%s" % (i, "v>=0" if x[3 + i] >= 0.0 else "v<0") for i in range(3)}
+
+
+def carlike_labels(x):
+    return {"carlike:x3>0" if x[3] > 0.0 else "carlike:x3<0" if x[3] < 0.0 else "carlike:x3==0"}
+
+
+def step_labels(m, x, u):
+    """Categories of ONE step evaluated at state x with effort u = K e."""
+    out = torque_labels(m.vmin2, x)
+    assert ("torque:direct" in out) == m.direct(x)
+    # ---- lane rows: thrusters, drag, car-like rule
+    out |= thruster_labels(m.thrusts(x, u), m.tmax)
+    out |= drag_labels(x)
+    out |= carlike_labels(x)
+    return out
+
+
+TORQUE_ARMS = ["torque:vx<0", "torque:v=+0", "torque:v=-0", "torque:slow", "torque:on-vmin2", "torque:vmin2+1ulp", "torque:direct",
+               "torque:reference", "torque:|vy|>|vx|", "torque:t=tan(pi/8)", "torque:t=tan(pi/8)+1ulp", "torque:t>tan(pi/8)",
+               "torque:t<=tan(pi/8)", "torque:arm-changes"]
+
+
+def torque_seeds(vmin):
+    """Body-frame velocities (v_x, v_y) that between them take every arm of TORQUE_ARMS (vmin: the system's torque_vmin)."""
+    vmin2 = vmin * vmin
+    seeds = [(-0.3, 0.1), (-0.5, -0.05), (-0.01, 0.3),                        # v_x < 0: only a seed state can have it
+             (0.0, 0.0), (-0.0, 0.0), (0.0, -0.0), (-0.0, -0.0),                 # atan2 of signed zeros
+             (vmin, 0.0), (0.0, vmin), (vmin, -0.0), (0.0, -vmin),               # |v|^2 == vmin^2: the reference's sequence
+             (0.005, 0.002), (0.002, -0.006),                                    # slower
+             (0.5, TAN_PI_8 / 2), (0.25, -TAN_PI_8 / 4), (0.5, up(TAN_PI_8) / 2), (0.25, -up(TAN_PI_8) / 4),
+             (0.5, 0.05), (0.1, 0.3), (0.05, -0.2), (0.3, 0.3), (0.2, up(0.2)),  # both sides of the fold, |v_y| > |v_x|
+             (0.0, 0.2), (0.0, -0.1), (-0.0, 0.15)]                              # v_x = 0 with a sway: direct, car-like rule idle
+    # |v|^2 one ulp above vmin^2: a sway v_y with fl(vmin^2 + v_y^2) = vmin^2 + 1 ulp
+    ulp = up(vmin2) - vmin2
+    for k in (0.75, 1.0, 1.25):
+        for sign in (1.0, -1.0):
+            vy = sign * math.sqrt(k * ulp)
+            if vmin * vmin + vy * vy == up(vmin2):
+                seeds.append((vmin, vy))
+    return seeds
+
+
 def required():
-    req = ["torque:vx<0", "torque:v=+0", "torque:v=-0", "torque:slow", "torque:on-vmin2", "torque:vmin2+1ulp", "torque:direct",
-           "torque:reference", "torque:|vy|>|vx|", "torque:t=tan(pi/8)", "torque:t=tan(pi/8)+1ulp", "torque:t>tan(pi/8)",
-           "torque:t<=tan(pi/8)", "torque:arm-changes"]
+    req = list(TORQUE_ARMS)
     req += ["thruster%d:%s-alone" % (j, w) for j in range(4) for w in ("upper", "lower")]
     req += ["drag%d:%s" % (i, w) for i in range(3) for w in ("v>=0", "v<0")]
     req += ["carlike:x3>0", "carlike:x3<0", "carlike:x3==0", "carlike:clamped"]
@@ -208,40 +260,26 @@ def required_sweep(V, O):
 Case = collections.namedtuple("Case", "pid target H FPR adaptive rollout labels")
 
 
-class World(object):
-    """kind "demo": demo_boat_advanced's own obstacle field; "directed": directed_table() with the buoy moved to the origin,
-    where a hull point's distance to it resolves to one ulp of the squared threshold."""
+class WorldBase(object):
+    """What every world of directed step cases shares (tests/packed_step_cases.py builds its worlds on it too): a system `s` of
+    the planar boats, its C oracle, the tree of parents, the case list with its coverage count, and the batches.  A subclass sets
+    `name`, `ident` (what plain() hands a child process to find the world again), `m` (its restated model: speed_ok) and
+    `required`, and provides classify() and _build()."""
 
-    def __init__(self, kind, V, O):
-        import lqrrt_amd
-        self.kind, self.V, self.O = kind, V, O
-        self.name = "%s-V%d-O%d" % (kind, V, O)
-        self.s = s = lqrrt_amd.systems.BoatAdvanced(0)
-        if hull(V) is not None:
-            s.vps = hull(V)
-        if kind == "directed":
-            table = directed_table(s.vps, O)
-            table[-1, :2] = 0.0
-            s.set_obstacles(table)
-        assert s.vps.shape[1] == V and len(s.obs) == O, (s.vps.shape, len(s.obs))
+    def _open(self, s):
+        self.s = s
         self.n, self.m_ = s.nstates, s.ncontrols
         self.o = SC.make_oracle(s, 4096)
         self.ops = R.coracle_ops(self.o, DT)
-        self.m = Model(s)
-        self.geo = F.CircleGeo(s.vps, s.obs)
+        self.geo = F.CircleGeo(s.vps, s.obs) if len(s.obs) else None
         self.states, self.K = [np.array(s.x0, dtype=np.float64)], [self.o.gain(s.x0, np.zeros(3))]
         self.cases = []
         self.coverage = collections.Counter()
-        self.required = (required() if kind == "demo" else []) + self.required_sweep()
-        self._build()
+
+    def _close(self):
         self.states, self.K = np.array(self.states), np.array(self.K)
         self.pID = np.arange(len(self.states), dtype=np.int32) - 1
         self.batches, self.batch_cases = self._batches()
-
-    def required_sweep(self):
-        if self.kind == "demo":                                # (centimetre coordinates tens of metres out: no one-ulp cases there)
-            return ["sweep:near=0", "sweep:near=1", "sweep:near-and-clear", "sweep:hit"]
-        return required_sweep(self.V, self.O)
 
     # -- the reference and its classification ---------------------------------------------------------------------------
     def gain(self, x):
@@ -249,7 +287,7 @@ class World(object):
 
     def sweep_labels(self, x):
         """What hull_hits meets at state x (empty when the speed box ends the test before it)."""
-        if not self.m.speed_ok(x):
+        if self.geo is None or not self.m.speed_ok(x):
             return set(), None
         g = self.geo
         c, s = F.portable_sincos(float(x[2]))
@@ -285,34 +323,6 @@ class World(object):
                 out.add("sweep:thr+1ulp")
         return out, not hits
 
-    def classify(self, x0, K0, xt, H, FPR, adaptive, r):
-        m, labels = self.m, set()
-        xt = np.asarray(xt, dtype=np.float64)
-        x, K = np.asarray(x0, dtype=np.float64), np.asarray(K0, dtype=np.float64)
-        arms = set()
-        for k in range(1, len(r.xall) + 1):
-            u = R.effort(K, self.ops.erf(xt, x))
-            xn = r.xall[k - 1]
-            if k <= len(r.xs):                                 # the step's arithmetic is in the outputs
-                st = step_labels(m, x, u)
-                if xn[3] == 0.0 and m.surge_before_clamp(x, u) < -1e-9:
-                    st.add("carlike:clamped")
-                arms.add("torque:direct" in st)
-                labels |= st
-            sw, clear = self.sweep_labels(xn)                  # the verdict on every evaluated state is in the outputs
-            labels |= sw
-            if clear is not None:                              # the restated sweep and the oracle agree
-                assert clear == self.ops.feasible(xn, u), (self.name, xn)
-            x, K = xn, (self.o.gain(xn, u) if k < len(r.xall) else K)
-        if len(arms) == 2:
-            labels.add("torque:arm-changes")
-        if H in HS:
-            if r.reason == ("horizon", H + 1):
-                labels.add("end:H%d:%s" % (H, "adaptive" if adaptive else "feasible"))
-            if r.reason == ("infeasible", H + 1) and not adaptive and FPR in FPRS:
-                labels.add("end:H%d:infeasible/FPR%g" % (H, FPR))
-        return labels
-
     def offer(self, x, K, xt, H=2, FPR=0.9, adaptive=False, keep=False):
         """Rolls the pair out with the reference; it becomes a case if it is the first or second of a required category (or keep)."""
         x, K, xt = (np.array(a, dtype=np.float64) for a in (x, K, xt))
@@ -324,9 +334,12 @@ class World(object):
             return False
         self.states.append(x)
         self.K.append(K)
-        self.cases.append(Case(len(self.states) - 1, xt, H, FPR, adaptive, r, labels))
+        self.cases.append(self.case_of(len(self.states) - 1, xt, H, FPR, adaptive, r, labels))
         self.coverage.update(labels)
         return True
+
+    def case_of(self, pid, xt, H, FPR, adaptive, r, labels):
+        return Case(pid, xt, H, FPR, adaptive, r, labels)
 
     def aim(self, x, u0, u1):
         """A target whose error asks the parent's own gain for the body-frame force (u0, u1), roughly."""
@@ -367,9 +380,66 @@ class World(object):
 
     def plain(self):
         """What a child process needs to run the batches (tests/test_steer_gpu.py run_batches)."""
-        return dict(kind=self.kind, V=self.V, O=self.O, dt=DT, states=self.states, K=self.K, pID=self.pID,
+        return dict(self.ident, dt=DT, states=self.states, K=self.K, pID=self.pID,
                     batches=[dict(H=b.H, FPR=b.FPR, adaptive=b.adaptive, tol=b.tol, goal=b.goal, buf=b.buf, parents=b.parents,
                                   targets=b.targets) for b in self.batches])
+
+
+class World(WorldBase):
+    """kind "demo": demo_boat_advanced's own obstacle field; "directed": directed_table() with the buoy moved to the origin,
+    where a hull point's distance to it resolves to one ulp of the squared threshold."""
+
+    def __init__(self, kind, V, O):
+        import lqrrt_amd
+        self.kind, self.V, self.O = kind, V, O
+        self.name = "%s-V%d-O%d" % (kind, V, O)
+        self.ident = dict(kind=kind, V=V, O=O)
+        s = lqrrt_amd.systems.BoatAdvanced(0)
+        if hull(V) is not None:
+            s.vps = hull(V)
+        if kind == "directed":
+            table = directed_table(s.vps, O)
+            table[-1, :2] = 0.0
+            s.set_obstacles(table)
+        assert s.vps.shape[1] == V and len(s.obs) == O, (s.vps.shape, len(s.obs))
+        self._open(s)
+        self.m = Model(s)
+        self.required = (required() if kind == "demo" else []) + self.required_sweep()
+        self._build()
+        self._close()
+
+    def required_sweep(self):
+        if self.kind == "demo":                                # (centimetre coordinates tens of metres out: no one-ulp cases there)
+            return ["sweep:near=0", "sweep:near=1", "sweep:near-and-clear", "sweep:hit"]
+        return required_sweep(self.V, self.O)
+
+    def classify(self, x0, K0, xt, H, FPR, adaptive, r):
+        m, labels = self.m, set()
+        xt = np.asarray(xt, dtype=np.float64)
+        x, K = np.asarray(x0, dtype=np.float64), np.asarray(K0, dtype=np.float64)
+        arms = set()
+        for k in range(1, len(r.xall) + 1):
+            u = R.effort(K, self.ops.erf(xt, x))
+            xn = r.xall[k - 1]
+            if k <= len(r.xs):                                 # the step's arithmetic is in the outputs
+                st = step_labels(m, x, u)
+                if xn[3] == 0.0 and m.surge_before_clamp(x, u) < -1e-9:
+                    st.add("carlike:clamped")
+                arms.add("torque:direct" in st)
+                labels |= st
+            sw, clear = self.sweep_labels(xn)                  # the verdict on every evaluated state is in the outputs
+            labels |= sw
+            if clear is not None:                              # the restated sweep and the oracle agree
+                assert clear == self.ops.feasible(xn, u), (self.name, xn)
+            x, K = xn, (self.o.gain(xn, u) if k < len(r.xall) else K)
+        if len(arms) == 2:
+            labels.add("torque:arm-changes")
+        if H in HS:
+            if r.reason == ("horizon", H + 1):
+                labels.add("end:H%d:%s" % (H, "adaptive" if adaptive else "feasible"))
+            if r.reason == ("infeasible", H + 1) and not adaptive and FPR in FPRS:
+                labels.add("end:H%d:infeasible/FPR%g" % (H, FPR))
+        return labels
 
     # -- construction ---------------------------------------------------------------------------------------------------
     def _build(self):
@@ -390,20 +460,7 @@ class World(object):
     def _torque_arm(self):
         vmin = self.s.torque_vmin
         assert vmin * vmin == self.m.vmin2
-        seeds = [(-0.3, 0.1), (-0.5, -0.05), (-0.01, 0.3),                        # v_x < 0: only a seed state can have it
-                 (0.0, 0.0), (-0.0, 0.0), (0.0, -0.0), (-0.0, -0.0),                 # atan2 of signed zeros
-                 (vmin, 0.0), (0.0, vmin), (vmin, -0.0), (0.0, -vmin),               # |v|^2 == vmin^2: the reference's sequence
-                 (0.005, 0.002), (0.002, -0.006),                                    # slower
-                 (0.5, TAN_PI_8 / 2), (0.25, -TAN_PI_8 / 4), (0.5, up(TAN_PI_8) / 2), (0.25, -up(TAN_PI_8) / 4),
-                 (0.5, 0.05), (0.1, 0.3), (0.05, -0.2), (0.3, 0.3), (0.2, up(0.2)),  # both sides of the fold, |v_y| > |v_x|
-                 (0.0, 0.2), (0.0, -0.1), (-0.0, 0.15)]                              # v_x = 0 with a sway: direct, car-like rule idle
-        # |v|^2 one ulp above vmin^2: a sway v_y with fl(vmin^2 + v_y^2) = vmin^2 + 1 ulp
-        ulp = up(self.m.vmin2) - self.m.vmin2
-        for k in (0.75, 1.0, 1.25):
-            for sign in (1.0, -1.0):
-                vy = sign * math.sqrt(k * ulp)
-                if vmin * vmin + vy * vy == up(self.m.vmin2):
-                    seeds.append((vmin, vy))
+        seeds = torque_seeds(vmin)
         for i, (vx, vy) in enumerate(seeds):
             for h in (0.0, 0.7, -2.5):
                 x = self._moving(self.OPEN, h, vx, vy, 0.05 * ((i % 3) - 1))
