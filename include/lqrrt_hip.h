@@ -420,6 +420,26 @@ int lqrrt_tree_clear_wait_multi(lqrrt_engine** engines, int n, const double* con
                                 const int32_t* L, const int32_t* D, const int32_t* start, const int32_t* waits,
                                 lqrrt_clear_wait_stats* out /*[n]*/, uint64_t* const* clear_host, uint64_t* const* dwell_host, void* stream);
 
+/* lqrrt_tree_clear_rects and lqrrt_tree_clear_rects_wait for n engines at once (lqrrt_amd.avoids_rects: a fleet of long hulls in a
+ * channel that checks its plans every tick against tracked hulls).  The rule is the one stated at those two calls (DESIGN.md
+ * sections 21 and 22), unchanged: member k's out[k] and per-node arrays are exactly what the one-tree call on engines[k] with
+ * tracks_host[k] ([L[k]][D[k]][3]), extents_host[k] ([D[k]][2]), L[k], D[k], start[k] (and waits[k]) gives -- every counter, every
+ * per-node value.  Everything else is lqrrt_tree_clear_multi's comment above with "radii" read as "extents" (DESIGN.md section
+ * 23): the output arrays of n pointers, ONE launch per stage whose grid spans the engines, one allocation per chunk of up to 32
+ * engines and one synchronise per call; members that pass the same tracks_host[k] and extents_host[k] pointers with equal L and D
+ * (the novice boats: and equal inflation) share one uploaded table, its extents included; nothing of any tree is written, all
+ * device memory of the call is transient and no engine's lqrrt_engine_footprint changes.  Synchronous.  The engines share the
+ * device and the model, n <= 128, no engine appears twice, none is generic.  EVERY argument of EVERY member is checked, in list
+ * order, before anything is allocated or enqueued, with lqrrt_tree_clear_rects's / lqrrt_tree_clear_rects_wait's codes and messages
+ * followed by "(engine k)"; a refused call writes nothing into any output. */
+int lqrrt_tree_clear_rects_multi(lqrrt_engine** engines, int n, const double* const* tracks_host, const double* const* extents_host,
+                                 const int32_t* L, const int32_t* D, const int32_t* start, lqrrt_clear_stats* out /*[n]*/,
+                                 int32_t* const* first_host, int32_t* const* dwell_host, void* stream);
+int lqrrt_tree_clear_rects_wait_multi(lqrrt_engine** engines, int n, const double* const* tracks_host, const double* const* extents_host,
+                                      const int32_t* L, const int32_t* D, const int32_t* start, const int32_t* waits,
+                                      lqrrt_clear_wait_stats* out /*[n]*/, uint64_t* const* clear_host, uint64_t* const* dwell_host,
+                                      void* stream);
+
 /* lqrrt_tree_clear and lqrrt_connect_search in one call (Planner.avoid(connect); DESIGN.md section 19;
  * tests/clear_connect_reference.py): when every goal hit of the tree is crossed by the discs, or only a long one is clear, which
  * node whose root path is clear reaches the goal by a short chain of goal-directed steers that stays clear too?  Everything of

@@ -4,7 +4,7 @@ MI355X build: code written against jnez71/lqRRT keeps its `import lqrrt` line an
 Tree and the native problem plugins (`systems`) are exported as well.
 """
 from lqrrt_amd import (Constraints, Planner, Tree, systems, update_plans, refine_plans, connect_goals, connect_vias,  # noqa: F401
-                       fleet_goal_costs, retargets, deconflict, avoids)
+                       fleet_goal_costs, retargets, deconflict, avoids, avoids_rects)
 
 __all__ = ["Constraints", "Planner", "Tree", "systems", "update_plans", "refine_plans", "connect_goals", "connect_vias",
-           "fleet_goal_costs", "retargets", "deconflict", "avoids"]
+           "fleet_goal_costs", "retargets", "deconflict", "avoids", "avoids_rects"]

@@ -18,13 +18,15 @@ through shared calls), retargets (every planner given a new goal from the tree i
 (prioritised planning over the trees as they stand: every planner picks the best plan of its tree that stays clear of the plans of
 those before it, Planner.avoid) and avoids (Planner.avoid for a fleet against shared or
 per-planner traffic: the trees of a group checked in one native call; with connect=goal_tries also the goal chains that stay clear
-of that traffic, searched for all trees in the same call and committed in one more).  Importing works without a GPU; computing does not.
+of that traffic, searched for all trees in the same call and committed in one more) and avoids_rects (Planner.avoid_rects for a
+fleet: the same against moving oriented rectangles, other hulls).  Importing works without a GPU; computing does not.
 """
 from .constraints import Constraints
-from .planner import Planner, update_plans, refine_plans, connect_goals, connect_vias, fleet_goal_costs, retargets, deconflict, avoids
+from .planner import (Planner, update_plans, refine_plans, connect_goals, connect_vias, fleet_goal_costs, retargets, deconflict, avoids,
+                      avoids_rects)
 from .tree import Tree
 from . import systems
 from . import dare
 
 __all__ = ["Constraints", "Planner", "Tree", "systems", "dare", "update_plans", "refine_plans", "connect_goals", "connect_vias",
-           "fleet_goal_costs", "retargets", "deconflict", "avoids"]
+           "fleet_goal_costs", "retargets", "deconflict", "avoids", "avoids_rects"]

@@ -122,6 +122,8 @@ SIGNATURES = {
     "lqrrt_tree_clear_rects_wait": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(ClearWaitStats), _P, _P, _P]),
     "lqrrt_tree_clear_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_tree_clear_wait_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lqrrt_tree_clear_rects_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lqrrt_tree_clear_rects_wait_multi": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lqrrt_tree_clear_connect": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, C.POINTER(ClearStats), C.POINTER(ClearConnectStats), _P, _P,
                                       _P]),
     "lqrrt_tree_clear_connect_multi": (_I, [_P, _I] + [_P] * 14),

@@ -91,6 +91,7 @@ static int fail(int code, const char* fmt, ...) {
 #include "engine_clear_rects.hpp" // ABI: tree_clear_rects (Planner.avoid_rects: the same against moving oriented rectangles, on engine_clear.hpp's host path)
 #include "engine_clear_rects_wait.hpp" // ABI: tree_clear_rects_wait (Planner.avoid_rects with max_wait: the rectangles for up to 64 departure delays at once)
 #include "engine_clear_multi.hpp" // ABI: tree_clear_multi / tree_clear_wait_multi (avoids, deconflict(batched): the same for several trees per launch)
+#include "engine_clear_rects_multi.hpp" // ABI: tree_clear_rects_multi / tree_clear_rects_wait_multi (avoids_rects: the rectangles for several trees per launch)
 #include "engine_connect.hpp"     // ABI: connect_search / connect_commit (Planner.connect_goal: goal chains from every tree node; + _multi)
 #include "engine_clear_connect.hpp" // ABI: tree_clear_connect (Planner.avoid(connect): goal chains from clear nodes that stay clear of the moving discs)
 #include "engine_clear_connect_multi.hpp" // ABI: tree_clear_connect_multi (avoids(connect): the same for several trees, on engine_clear_multi.hpp's host path)

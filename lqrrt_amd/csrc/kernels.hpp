@@ -223,6 +223,7 @@ __device__ __forceinline__ double quad_cost(const double* e, const double* Sd) {
 #include "clear_connect_multi.hpp" // k_clear_connect_multi_seed / k_clear_connect_search_multi (avoids(connect): the same for several trees per launch)
 #include "clear_rects.hpp" // k_clear_rects_check                                     (Planner.avoid_rects: the clearance query against moving oriented rectangles)
 #include "clear_rects_wait.hpp" // k_clear_rects_wait_check                           (Planner.avoid_rects with max_wait: the same for up to 64 departure delays at once)
+#include "clear_rects_multi.hpp" // k_clear_rects_check_multi / k_clear_rects_wait_check_multi (avoids_rects: both rectangle queries for several trees per launch)
 #include "reach.hpp"      // k_reach_search                                           (Planner.goal_costs / retarget: those chains to MANY goals per launch)
 #include "reach_multi.hpp" // k_reach_search_multi / k_reach_commit_multi                    (fleet_goal_costs / retargets: several trees per launch)
 #include "connect_via.hpp" // k_connect_via_search / k_connect_via_commit             (Planner.connect_via: the same through a list of waypoints)

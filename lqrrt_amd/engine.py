@@ -431,6 +431,26 @@ class Engine(object):
                                    per_node)
 
     @staticmethod
+    def tree_clear_rects_multi(engines, tables, extents, starts, per_node=False):
+        """tree_clear_rects for n engines in one native call (lqrrt_tree_clear_rects_multi; csrc/clear_rects_multi.hpp), as
+        tree_clear_multi: every stage one kernel launch that spans the engines, one allocation per chunk of 32 and one wait per
+        call.  `tables`, `extents`, `starts`: one entry per engine, each what rect_table takes; engines that are handed the SAME
+        table and extents objects (arrays, as rect_table returns them) share one upload.  Returns, per engine, exactly what its own
+        tree_clear_rects(tables[k], extents[k], starts[k], per_node) returns.  The engines share device and model.  Every argument
+        of every engine is checked before anything is launched (ValueError / NativeError as tree_clear_rects, the message naming
+        the engine); nothing of any tree is written."""
+        return Engine._clear_multi("lqrrt_tree_clear_rects_multi", nat.ClearStats, np.int32, engines, tables, extents, starts, None,
+                                   per_node, rects=True)
+
+    @staticmethod
+    def tree_clear_rects_wait_multi(engines, tables, extents, starts, waits, per_node=False):
+        """tree_clear_rects_wait for n engines in one native call (lqrrt_tree_clear_rects_wait_multi), as tree_clear_rects_multi;
+        `waits`: one count for all or one per engine, each 1 .. 64.  Returns, per engine, exactly what its own
+        tree_clear_rects_wait returns."""
+        return Engine._clear_multi("lqrrt_tree_clear_rects_wait_multi", nat.ClearWaitStats, np.uint64, engines, tables, extents, starts,
+                                   waits, per_node, rects=True)
+
+    @staticmethod
     def tree_clear_connect_multi(engines, tables, radii, starts, horizons, tries=8, nodes=None, per_node=False):
         """tree_clear_connect for n engines in one native call (lqrrt_tree_clear_connect_multi; csrc/clear_connect_multi.hpp):
         tree_clear_multi's stages, then ONE launch that seeds every tree's key and ONE search launch over the candidates of all
@@ -445,17 +465,19 @@ class Engine(object):
                                    per_node, connect=(horizons, tries, nodes))
 
     @staticmethod
-    def _clear_multi(call, stats, dtype, engines, tables, radii, starts, waits, per_node, connect=None):
+    def _clear_multi(call, stats, dtype, engines, tables, radii, starts, waits, per_node, connect=None, rects=False):
         """tree_clear_multi (`waits` None), tree_clear_wait_multi and tree_clear_connect_multi (`connect`: horizons, tries, nodes):
         every engine's arguments checked in the solo calls' order, one native call, and per engine what _clear / tree_clear_connect
-        returns."""
+        returns.  `rects`: the tables are rect_table's and `radii` holds the extents (tree_clear_rects_multi,
+        tree_clear_rects_wait_multi); the rest is the same."""
+        build, second = (Engine.rect_table, "extents") if rects else (Engine.track_table, "radii")
         engines = list(engines)
         n = len(engines)
         if n < 1:
             raise ValueError("no engines")
         tables, radii, starts = list(tables), list(radii), list(starts)
         if not len(tables) == len(radii) == len(starts) == n:
-            raise ValueError("expected one track table, one radii array and one start per engine")
+            raise ValueError("expected one track table, one %s array and one start per engine" % second)
         if waits is not None:
             waits = [waits] * n if isinstance(waits, (int, np.integer)) else list(waits)
             if len(waits) != n:
@@ -466,11 +488,11 @@ class Engine(object):
         for k in range(n):
             key = (id(tables[k]), id(radii[k]))
             if key not in seen:
-                seen[key] = Engine.track_table(tables[k], radii[k], 0)[:2]
+                seen[key] = build(tables[k], radii[k], 0)[:2]
             tabs.append(seen[key])
             if int(starts[k]) != starts[k] or int(starts[k]) < 0:
                 raise ValueError("start must be an integer >= 0.")
-        Ls =np.array([t.shape[0] for t, _ in tabs], dtype=np.int32)
+        Ls = np.array([t.shape[0] for t, _ in tabs], dtype=np.int32)
         Ds = np.array([t.shape[1] for t, _ in tabs], dtype=np.int32)
         st0 = np.array([int(s) for s in starts], dtype=np.int64)
         if np.any(st0 > 2 ** 31 - 1):

@@ -896,8 +896,8 @@ class Planner:
         (size, hits, clear_hits, clear_now, best_end, best_wait, best_steps, best_arrival, plan_first), the adoption with
         `best_wait` copies of the first row in front and `plan_wait`, and the one more plain call for plan_first when the current
         plan does not hold are avoid's with max_wait.  With max_wait = 0 the call, its cost and its dict are what they were.
-        Not covered (DESIGN.md sections 21 and 22): connect, a fleet launch, deconflict(extents=...) with max_wait, discs and
-        rectangles in one call, convex polygons.
+        A fleet asks avoids_rects, which shares the native calls.  Not covered (DESIGN.md sections 21 to
+        23): connect, deconflict(extents=...) with batched or max_wait, discs and rectangles in one call, convex polygons.
         """
         if self.callback_mode:                                      # (as avoid)
             raise NotImplementedError("avoid_rects: in callback mode the feasibility test is the user's Python function; the device "
@@ -1734,23 +1734,25 @@ def _fleet_avoid_runs(name, planners):
         raise ValueError(str(ex).replace("avoid:", name + ":").replace("refine_plan:", name + ":"))
 
 
-def _avoids_query(planners, runs, tables, radii, starts, max_wait):
+def _avoids_query(planners, runs, tables, radii, starts, max_wait, query=None):
     """The device calls of avoid for the planners that have a run, batched: per planner (counters, first, dwell) -- first / dwell the
     plain query's per-node arrays at the current plan's departure, or None where the wait query shows that plan to be clear -- and
     None for a planner without a run.  One native call per group of _fleet_groups, and with max_wait ONE more (the plain query for
-    the planners whose current plan is not clear).  Touches no planner.  Returns (results, native calls made)."""
+    the planners whose current plan is not clear).  Touches no planner.  Returns (results, native calls made).  `query`: the pair
+    of Engine calls (plain, wait) that answer; None: the discs' (tree_clear_multi, tree_clear_wait_multi).  avoids_rects passes the
+    rectangles' pair, and `radii` then holds the extents."""
+    plain_multi, wait_multi = (Engine.tree_clear_multi, Engine.tree_clear_wait_multi) if query is None else query
     res, calls = [None] * len(planners), 0
     for members in _fleet_groups(planners, runs):
         pick = lambda seq, ks: [seq[k] for k in ks]
         engines = [planners[k]._engine for k in members]
         if max_wait == 0:
-            got = Engine.tree_clear_multi(engines, pick(tables, members), pick(radii, members), pick(starts, members), per_node=True)
+            got = plain_multi(engines, pick(tables, members), pick(radii, members), pick(starts, members), per_node=True)
             calls += 1
             for k, g in zip(members, got):
                 res[k] = g
             continue
-        got = Engine.tree_clear_wait_multi(engines, pick(tables, members), pick(radii, members), pick(starts, members), max_wait + 1,
-                                           per_node=True)
+        got = wait_multi(engines, pick(tables, members), pick(radii, members), pick(starts, members), max_wait + 1, per_node=True)
         calls += 1
         again = []
         for k, (out, clear, dwell_ok) in zip(members, got):
@@ -1758,8 +1760,8 @@ def _avoids_query(planners, runs, tables, radii, starts, max_wait):
             if not planners[k]._avoid_plan_holds(runs[k], clear, dwell_ok, max_wait):
                 again.append(k)
         if again:                                                   # the time of their plans' first conflict: the plain query, once for all
-            got = Engine.tree_clear_multi([planners[k]._engine for k in again], pick(tables, again), pick(radii, again),
-                                          [starts[k] + planners[k].plan_wait for k in again], per_node=True)
+            got = plain_multi([planners[k]._engine for k in again], pick(tables, again), pick(radii, again),
+                              [starts[k] + planners[k].plan_wait for k in again], per_node=True)
             calls += 1
             for k, (_, first, dwell) in zip(again, got):
                 res[k] = (res[k][0], first, dwell)
@@ -1818,6 +1820,51 @@ def avoids(planners, tracks, radii, start=0, adopt=True, max_wait=0, connect=0):
     if connect:
         return _avoids_connect(planners, runs, [t[0] for t in tabs], [t[1] for t in tabs], start, adopt, connect)
     got, _ = _avoids_query(planners, runs, [t[0] for t in tabs], [t[1] for t in tabs], [start] * n, max_wait)
+    return [None if run is None else p._avoid_end(run, g[0], g[1], g[2], start, adopt) for p, run, g in zip(planners, runs, got)]
+
+
+def avoids_rects(planners, tracks, extents, start=0, adopt=True, max_wait=0):
+    """
+    avoid_rects for a fleet, as avoids is avoid for a fleet: every planner gets exactly what its own avoid_rects(tracks, extents,
+    start, adopt, max_wait) returns and leaves -- the dict (plan_first included), the adopted plan with its wait rows, plan_wait, T,
+    t_seq, plan_reached_goal, the dropped finish_on_goal tail, None for a planner without a tree of its own on the device -- but the
+    device calls are shared: the planners of one (device, native system type) form a group, and a group's trees are checked in ONE
+    native call (Engine.tree_clear_rects_multi / tree_clear_rects_wait_multi, csrc/clear_rects_multi.hpp: every stage one launch that
+    spans the trees), in slices of 128.  With `max_wait` the planners whose current plan is not clear get the plain query at their
+    plan's departure, for plan_first, in ONE further call per group.  `tracks`, `extents`: one set for everybody, as avoid_rects
+    takes it -- the shared-traffic case: the table (poses and extents) is built and uploaded once per launch, not once per tree --
+    or a list with one such entry per planner (tracks: a list of len(planners) entries, each an array (L, D, 3) or a list of D
+    arrays (L_d, 3); extents: the matching list).  The trees are never modified.  Both fleets run one path (_avoids_query).
+
+    Refused before any planner is touched: everything avoid_rects refuses (a changed goal, which avoid_rects refuses with
+    RuntimeError, is a ValueError here, as in the other fleet calls), a planner that appears twice, an object that is no Planner,
+    per-planner tracks without per-planner extents.  Callback mode raises NotImplementedError.  There is no `connect`: there is no
+    rectangle connect yet.  Not covered: deconflict(extents=...) with batched or max_wait, connect against
+    rectangles, discs and rectangles in one call, convex polygons.
+    """
+    planners = list(planners)
+    n = len(planners)
+    if len(set(id(p) for p in planners)) != n:
+        raise ValueError("avoids_rects: a planner appears twice.")
+    for k, p in enumerate(planners):
+        if not isinstance(p, Planner):
+            raise ValueError("avoids_rects: expected Planner objects.")
+        if p.callback_mode:
+            raise NotImplementedError("avoids_rects: planner %d is in callback mode; the device cannot call its Python feasibility test." % k)
+    per = n > 0 and isinstance(tracks, (list, tuple)) and len(tracks) == n and all(isinstance(t, (list, tuple)) or np.ndim(t) == 3 for t in tracks)
+    if per:
+        if not isinstance(extents, (list, tuple, np.ndarray)) or len(extents) != n:
+            raise ValueError("avoids_rects: tracks per planner need extents per planner (a list of %d entries)." % n)
+        tabs = [Engine.rect_table(tracks[k], extents[k], start) for k in range(n)]
+    else:
+        tabs = [Engine.rect_table(tracks, extents, start)] * n
+    max_wait = Engine.wait_count(max_wait, "max_wait", 0, 63)
+    if not planners:
+        return []
+    start = tabs[0][2]
+    runs = _fleet_avoid_runs("avoids_rects", planners)
+    got, _ = _avoids_query(planners, runs, [t[0] for t in tabs], [t[1] for t in tabs], [start] * n, max_wait,
+                           (Engine.tree_clear_rects_multi, Engine.tree_clear_rects_wait_multi))
     return [None if run is None else p._avoid_end(run, g[0], g[1], g[2], start, adopt) for p, run, g in zip(planners, runs, got)]
 
 
